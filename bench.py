@@ -30,10 +30,16 @@ Output: ONE JSON line on rank 0 with the driver's contract fields plus
   roofline     — dominant kernel of the workload: algorithmic bytes per launch / HIP-event time of the launches
                  on the stream they run on, vs 8 TB/s HBM; `traffic` = HBM bytes per launch from the committed
                  rocprofv3 PMC summaries of the same command (profiles/), corrected as MI355X_MICROARCH.md says
+A plain run does only what that line needs: set-up, W warm-up steps, the K timed steps, the line.  With --full it also
+measures and checks what takes runs of its own:
   cpu_baseline — the real reference NLopt (oracle/_ref, kind "reference") or the C port (kind "port") timed
                  single-threaded on this host on a bounded sample of the same workload
   gens_to_ftol — (crs) numevals/pop at NLOPT_FTOL_REACHED on the small configuration where the CPU reference can
                  reach it, with the reference's golden value beside it.
+  pinned_run   — the timed run against the real reference's run of the same problem (tests/golden/)
+  (crs, N = 1) other_sizes, other_workloads, nlopt_optimize_end_to_end; (crs, N > 1) config5_one_job
+--dump-outputs DIR writes what the timed run hands its caller after the last step (best point x, minf, numevals) as
+DIR/<name>.npy, float64; the inputs are fixed by the arguments (seed, sizes), so two builds can be compared output for output.
 """
 import argparse
 import ctypes as C
@@ -55,7 +61,12 @@ STUCK = []                     # set when the one-job config-5 block of a multi-
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--config5-pop", type=int, default=1000000, help="population of the one-job CRS block reported at --gpus > 1")
+    ap.add_argument("--full", action="store_true",
+                    help="also the CPU baselines, the pins against the reference, gens-to-ftol, the other sizes / workloads, the end-to-end "
+                         "call and (--gpus > 1) the config-5 block; a plain run times the headline alone")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the timed run returned (x, minf, numevals) as DIR/<name>.npy (float64)")
+    ap.add_argument("--config5-pop", type=int, default=1000000, help="population of the one-job CRS block reported at --gpus > 1 with --full")
     ap.add_argument("--config5-n", type=int, default=4096)
     ap.add_argument("--no-config5", action="store_true")
     ap.add_argument("--config5-timeout", type=int, default=300)
@@ -75,11 +86,11 @@ def parse():
     ap.add_argument("--seed", type=int, default=42)
     ap.add_argument("--max-spec", type=int, default=0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--headline-only", action="store_true", help="crs: skip the other sizes / workloads / end-to-end call (tuning runs)")
+    ap.add_argument("--headline-only", action="store_true", help="crs with --full: skip the other sizes / workloads / end-to-end call (tuning runs)")
     ap.add_argument("--cpu-sample-pop", type=int, default=0)
     ap.add_argument("--cpu-sample-trials", type=int, default=400)
     ap.add_argument("--detail", default="", metavar="PATH",
-                    help="where the FULL record goes (host_split, phases, sample strings, latency models ...); default gpurun_out/bench_detail.json. "
+                    help="where the FULL record goes (host_split, phases, sample strings, latency models ...); not written without it. "
                          "The printed line is the compact form of it (kept below the 8 KB of stdout a driver record keeps)")
     ap.add_argument("--full-line", action="store_true", help="print the full record as the JSON line (what rounds 1-4 printed)")
     a = ap.parse_args()
@@ -287,14 +298,19 @@ def main():
     else:
         out = bench_generational(a, nlopt_amd, L, rank, world, dist, sync_all, reduce)
     if rank == 0:
-        path = a.detail or os.path.join(ROOT, "gpurun_out", "bench_detail.json")
-        try:
-            os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-            with open(path, "w") as fh:
-                json.dump(out, fh, indent=1)
-            out["detail"] = os.path.relpath(path, ROOT)
-        except OSError:
-            pass
+        outputs = out.pop("outputs")
+        if a.dump_outputs:
+            os.makedirs(a.dump_outputs, exist_ok=True)
+            for name, v in outputs.items():
+                np.save(os.path.join(a.dump_outputs, name + ".npy"), np.asarray(v, dtype=np.float64).reshape(-1))
+        if a.detail:
+            try:
+                os.makedirs(os.path.dirname(os.path.abspath(a.detail)), exist_ok=True)
+                with open(a.detail, "w") as fh:
+                    json.dump(out, fh, indent=1)
+                out["detail"] = os.path.relpath(a.detail, ROOT)
+            except OSError:
+                pass
         print(json.dumps(out if a.full_line else compact_line(out)), flush=True)
     if STUCK:                              # a hung collective thread is still alive: no barrier, no orderly teardown
         os._exit(0)
@@ -402,8 +418,8 @@ def crs_measure(nlopt_amd, L, obj, n, pop, seed, warmup, steps, evals_per_step, 
     sync_all()
     dt = time.perf_counter() - t0
     st1, ev1 = o.stats(), o.get_numevals()
-    fret = L.nlopt_amd_crs_close(s)
-    return dict(dt=dt, evals=ev1 - ev0, st0=st0, st1=st1, t_init=t_init, fret=int(fret), minf=minf.value, numevals=int(ev1))
+    fret = L.nlopt_amd_crs_close(s)          # writes the best point into x and minf
+    return dict(dt=dt, evals=ev1 - ev0, st0=st0, st1=st1, t_init=t_init, fret=int(fret), minf=minf.value, numevals=int(ev1), x=x)
 
 
 def pinned_to_reference(m, n, pop, obj, seed):
@@ -604,7 +620,7 @@ def bench_crs(a, nlopt_amd, L, rank, world, sync_all, reduce):
             dt, st0, st1, t_init, fret = m["dt"], m["st0"], m["st1"], headline_one_job["t_init"], m["fret"]
             dt_max, evals_all = headline_one_job["dt"], headline_one_job["evals"]
     sharded = bool(world > 1 and headline_one_job and "error" not in headline_one_job)
-    if world > 1 and not a.no_config5 and not STUCK:
+    if world > 1 and a.full and not a.no_config5 and not STUCK:
         # BASELINE.json config 5 is the only CRS configuration with multi-GPU work in it: ONE job over all ranks.
         # It runs under a watchdog: the replica value above is already measured, and a communicator that never comes up (RCCL's
         # bootstrap did not return on one box in round 1) must not take the whole line with it
@@ -698,12 +714,13 @@ def bench_crs(a, nlopt_amd, L, rank, world, sync_all, reduce):
                        "list_refresh_s": st1["t_list_refresh_s"] - st0["t_list_refresh_s"]},
         "init": {"evals": pop, "seconds": t_init, "init_evals_per_s": pop / t_init},
         "final_result": int(fret), "minf": m["minf"],
+        "outputs": {"x": m["x"], "minf": m["minf"], "numevals": m["numevals"]},
     }
-    if world == 1 or sharded:
+    if a.full and (world == 1 or sharded):
         pin = pinned_to_reference(m, n, pop, a.obj, a.seed)
         if pin:
             out["pinned_run"] = pin
-    if world == 1 and (n, pop, a.obj) == (4096, 100000, "griewank") and not a.headline_only:
+    if a.full and world == 1 and (n, pop, a.obj) == (4096, 100000, "griewank") and not a.headline_only:
         # north_star asks for n in {64, 512, 4096}: the two smaller sizes (512 = BASELINE config 2), shorter runs, same contract
         out["other_sizes"] = {}
         for n2 in (512, 64):
@@ -745,11 +762,12 @@ def bench_crs(a, nlopt_amd, L, rank, world, sync_all, reduce):
             out["replicas_note"] = ("the one-job run failed (see one_job): value = sum over %d independent replicas of the metric configuration, scaling weak" % world)
         out["replicas"] = replicas
         out["config5_one_job"] = one_job
-    try:
-        out["gens_to_ftol"] = gens_to_ftol()
-    except Exception as e:        # the headline line must still be printed
-        out["gens_to_ftol"] = {"error": repr(e)}
-    if world == 1 and (n, pop, a.obj) == (4096, 100000, "griewank") and not a.headline_only:
+    if a.full:
+        try:
+            out["gens_to_ftol"] = gens_to_ftol()
+        except Exception as e:        # the headline line must still be printed
+            out["gens_to_ftol"] = {"error": repr(e)}
+    if a.full and world == 1 and (n, pop, a.obj) == (4096, 100000, "griewank") and not a.headline_only:
         # SURVEY.md §8d defines the metric on nlopt_optimize(): one whole call (population initialisation included) on record
         try:
             out["nlopt_optimize_end_to_end"] = crs_end_to_end(nlopt_amd, a.obj, n, pop, a.seed, 20000)
@@ -768,9 +786,10 @@ def bench_crs(a, nlopt_amd, L, rank, world, sync_all, reduce):
                 if exact:
                     b.no_cpu_baseline = True          # the same CPU run as the default mode's line
                 out["other_workloads"][key] = bench_generational(b, nlopt_amd, L, 0, 1, None, sync_all, reduce)
+                out["other_workloads"][key].pop("outputs")
             except (Exception, SystemExit) as e:
                 out["other_workloads"][wl] = {"error": repr(e)}
-    if not a.no_cpu_baseline and world == 1:                  # the CPU baseline is timed on rank 0 of the 1-GPU run only
+    if a.full and not a.no_cpu_baseline and world == 1:       # the CPU baseline is timed on rank 0 of the 1-GPU run only
         try:
             # the headline's sample runs at the metric's OWN population (12 s of untimed reference initialisation at pop = 1e5, n = 4096;
             # round-5 verdict, weak 6: the rate had only ever been shown to be independent of pop on the survey's machine)
@@ -913,8 +932,9 @@ def bench_generational(a, nlopt_amd, L, rank, world, dist, sync_all, reduce):
                      "avg_launch_ms": 1e3 * t_dom / launches if launches else None,
                      "avg_algorithmic_bytes_per_launch": bytes_dom / launches if launches else None},
         "phases": phases, "total_seconds_incl_setup": t_total, "final_result": int(ret), "minf": minf,
+        "outputs": {"x": x, "minf": minf, "numevals": o.get_numevals()},
     }
-    if world == 1:
+    if a.full and world == 1:
         try:
             if a.workload == "isres":
                 out["pinned_run"] = pinned_isres(n, pop, a.obj, a.seed, ncon, o.get_numevals(), minf, o.stats()["mt_words"])
@@ -933,7 +953,7 @@ def bench_generational(a, nlopt_amd, L, rank, world, dist, sync_all, reduce):
         out["roofline"] = roof_extra
     if comm is not None:
         out["collectives"] = comm.counters()
-    if not a.no_cpu_baseline and world == 1:
+    if a.full and not a.no_cpu_baseline and world == 1:
         try:
             if a.workload == "isres":
                 out["cpu_baseline"] = cpu_baseline_isres(a.obj, n, a.cpu_sample_pop or pop, a.seed, ncon)

@@ -23,7 +23,8 @@ def pytest_configure(config):
         if not os.path.exists(os.path.join(ref, "libnlopt_ref.so")):
             subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "oracle"), "ref"], check=True)
         if not os.path.exists(os.path.join(ref, "testopt_amd")) or not os.path.exists(os.path.join(ref, "t_bounded_amd")) \
-                or not os.path.exists(os.path.join(ref, "t_tutorial_amd")) or not os.path.exists(os.path.join(ref, "cpp_functor_amd")):
+                or not os.path.exists(os.path.join(ref, "t_tutorial_amd")) or not os.path.exists(os.path.join(ref, "cpp_functor_amd")) \
+                or not os.path.exists(os.path.join(ref, "test", "t_memoize.py")):
             subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "oracle"), "cpptest"], check=True)
 
 

@@ -20,9 +20,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF = os.path.join(ROOT, "oracle", "_ref", "libnlopt_ref.so")
 EMU = os.path.join(ROOT, "oracle", "libnlopt_amd_emu.so")
 SHIM = os.path.join(ROOT, "tests", "pyapi")
-REFTEST = "/root/reference/test"
+REFTEST = os.path.join(ROOT, "oracle", "_ref", "test")          # the reference's scripts, staged by `make -C oracle cpptest`
 need = pytest.mark.skipif(not (os.path.exists(REF) and os.path.exists(EMU)), reason="oracle/_ref or the emulated library not built")
-need_reftest = pytest.mark.skipif(not os.path.isdir(REFTEST), reason="the reference's test scripts are not on this machine")
+need_reftest = pytest.mark.skipif(not os.path.isdir(REFTEST), reason="oracle/_ref/test not built (the reference's test scripts)")
 
 
 def run(script, *args, library=None, timeout=900):
