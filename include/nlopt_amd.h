@@ -550,7 +550,10 @@ int nla_cobyla_fits(int n);                                    /* 1: that fits a
 /* replaces: cobyla_minimize (cobyla.c:181-271) as nlopt_optimize(LN_COBYLA) reaches it (optimize.c:836-851, with the memoized best
  * point of :450-508,1064-1071) for `count` independent starts at once, one WAVEFRONT per start, compiled-in device objectives only.
  * X: count x ld, starts in, results out; dx: the initial step (n, device) or NULL = nlopt_set_default_initial_step per start
- * (options.c:921-946); out[i] = (f, nlopt_result, objective calls, the same, 0).  Fails (hipErrorInvalidValue) when !nla_cobyla_fits(n). */
+ * (options.c:921-946); out[i] = (f, nlopt_result, objective calls, the same, 0).  Fails (hipErrorInvalidValue) when !nla_cobyla_fits(n).
+ * Precondition: lb[j] < ub[j] for every j — a fixed coordinate (lb[j] == ub[j]) is not eliminated here as the reference eliminates it
+ * (optimize.c:412-445): every search of such a box is refused, out[i] = (HUGE_VAL, NLOPT_INVALID_ARGS, 0, 0, 0), with no objective
+ * call and X unchanged.  Callers run such boxes through nlopt_optimize(LN_COBYLA), which eliminates (mlsl_driver.c does). */
 int nla_k_cobyla_batch(int obj, int n, int ld, int count, const double *lb, const double *ub, const double *dx, double *X,
                        double *work, int *iwork, const nla_cobyla_params *params, nla_lbfgs_result *out, void *stream);
 

@@ -449,7 +449,18 @@ __global__ __launch_bounds__(CW_LANES) void cobyla_batch_kernel(int n, int ld, i
     int i, j, k, m = 0;
 
     /* the number of rows first: the finite bounds (cobyla.c:233-241) */
-    for (j = 0; j < n; ++j) { if (!cw_isinf(lb[j])) ++m; if (!cw_isinf(ub[j])) ++m; }
+    int fixed = 0;
+    for (j = 0; j < n; ++j) { if (!cw_isinf(lb[j])) ++m; if (!cw_isinf(ub[j])) ++m; if (lb[j] == ub[j]) fixed = 1; }
+    /* a coordinate with lb == ub: the reference eliminates it in front of COBYLA (optimize.c:412-445, elimdim), this kernel does not
+     * (its initial simplex would have a zero edge there, SIMI = 1/0) — the search is refused before any objective call: INVALID_ARGS,
+     * no evaluation, the start left as it was.  (Every lane ran the same loop: the whole wavefront leaves here together.) */
+    if (fixed) {
+        if (lane == 0) {
+            out[inst].f = __builtin_huge_val(); out[inst].ret = CW_INVALID_ARGS; out[inst].nevals = 0; out[inst].iterm = 0; out[inst].cols = 0;
+            if (P.done) __hip_atomic_fetch_add(P.done, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        return;
+    }
     cw_ws W;
     {
         const int v = cw_vlen(n, m);

@@ -466,6 +466,10 @@ nlopt_result nla_mlsl_minimize(nlopt_opt opt, int n, nlopt_func f, void *f_data,
     D.obj = D.ev.kind == NLA_EVAL_DEVICE ? D.ev.obj : -1;
     cob_dev = use_cobyla && D.ev.kind == NLA_EVAL_DEVICE && nla_cobyla_fits(n) && !(opt && nlopt_get_param(opt, "amd_cobyla_host", 0) != 0) &&
               !nlopt_get_param(local_opt, "amd_cobyla_host", 0);
+    /* a fixed coordinate (lb[i] == ub[i]): the reference's nlopt_optimize_limited eliminates it in front of each COBYLA search
+     * (optimize.c:412-445), the device kernel does not (it refuses such a box, include/nlopt_amd.h) — the host algorithm, whose
+     * nlopt_optimize eliminates like the reference (api_optimize.c fix_applies) */
+    for (i = 0; cob_dev && i < n; ++i) if (lb[i] == ub[i]) cob_dev = 0;
     if (cob_dev) use_cobyla = 0;              /* from here on `use_cobyla` means: the host algorithm */
     host = D.ev.kind == NLA_EVAL_HOST || use_cobyla;
     sw.f = f; sw.f_data = f_data; sw.sign = -1.; sw.nevals_p = NULL;

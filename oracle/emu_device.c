@@ -631,6 +631,11 @@ int nla_k_cobyla_batch(int obj, int n, int ld, int count, const double *lb, cons
     (void) work; (void) iwork; (void) st;
     if (!nla_cobyla_fits(n)) return EMU_ERR;                 /* (as the kernel: the state of a search must fit the LDS) */
     nla_emu_last_exact = P->exact;
+    for (int j = 0; j < n; ++j)                               /* (as the kernel: a fixed coordinate is refused, not eliminated — nlopt_optimize would eliminate it) */
+        if (lb[j] == ub[j]) {
+            for (int i = 0; i < count; ++i) { out[i].f = HUGE_VAL; out[i].ret = NLOPT_INVALID_ARGS; out[i].nevals = out[i].iterm = 0; out[i].cols = 0; }
+            return 0;
+        }
     for (int i = 0; i < count; ++i) {
         emu_cob_obj o = { obj & 0xff, (P->sign == 0. ? 1. : P->sign) * ((obj & 0x100) ? -1. : 1.) };
         nlopt_opt loc = nlopt_create(NLOPT_LN_COBYLA, (unsigned) n);

@@ -450,7 +450,7 @@ class MlslTrace(C.Structure):
 
 
 def run_port_mlsl(obj, n, nsamples, seed, maxeval=0, stopval=None, local_ftol_rel=1e-8, local_xtol_rel=0.0, local_ftol_abs=0.0,
-                  local_maxeval=0, mf=0, x0=None, record=True, lds=False, local="lbfgs", local_params=None):
+                  local_maxeval=0, mf=0, x0=None, record=True, lds=False, local="lbfgs", local_params=None, lb=None, ub=None):
     L = port()
     L.orc_mlsl_set_lds(int(lds))
     L.orc_mlsl_minimize.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double),
@@ -458,7 +458,8 @@ def run_port_mlsl(obj, n, nsamples, seed, maxeval=0, stopval=None, local_ftol_re
                                     C.POINTER(OrcLocal), C.POINTER(MlslTrace)]
     xs, lo, hi = golden_x0(obj, n)
     x = np.array(xs if x0 is None else x0, dtype=np.float64)
-    lb, ub = np.full(n, lo), np.full(n, hi)
+    lb = np.full(n, lo) if lb is None else np.array(lb, dtype=np.float64)
+    ub = np.full(n, hi) if ub is None else np.array(ub, dtype=np.float64)
     st = OrcStop()
     L.orc_stop_default(C.byref(st), n)
     st.maxeval = maxeval
@@ -535,12 +536,16 @@ def ref_sobol_points(sdim, skip_n, count, lb=None, ub=None):
 
 
 def run_ref_mlsl(obj, n, nsamples, seed, alg=38, local_ftol_rel=1e-8, local_xtol_rel=0.0, local_ftol_abs=0.0, local_maxeval=0, mf=0,
-                 local="lbfgs", local_params=None, **kw):
+                 local="lbfgs", local_params=None, lb=None, ub=None, **kw):
     """the REAL reference's G_MLSL (38) with an LD_LBFGS (11) or LD_MMA (24) local optimiser; local=None: no local optimiser is
     set and the tolerances go on the global object, from which the dispatcher builds its default (optimize.c:763-777)"""
     def setup(R, opt):
         R.nlopt_set_vector_storage.argtypes = [C.c_void_p, C.c_uint]
         R.nlopt_set_param.argtypes = [C.c_void_p, C.c_char_p, C.c_double]
+        if lb is not None:
+            R.nlopt_set_lower_bounds(opt, dptr(np.array(lb, dtype=np.float64)))
+        if ub is not None:
+            R.nlopt_set_upper_bounds(opt, dptr(np.array(ub, dtype=np.float64)))
         if local is None:
             return
         loc = R.nlopt_create(24 if local == "mma" else 11, n)

@@ -198,3 +198,54 @@ def test_gn_mlsl_with_a_registered_objective_min_and_max(alg, obj, n, maximise):
         out.append((ret, minf.value, x.copy(), lib.nlopt_get_numevals(opt)))
         lib.nlopt_destroy(opt)
     assert out[0][0] == out[1][0] and out[0][1] == out[1][1] and np.array_equal(out[0][2], out[1][2]) and out[0][3] == out[1][3], out
+
+
+def play_mlsl_fixed(L, draw):
+    """GN_MLSL(_LDS) with 1 .. n-1 coordinates fixed (lb == ub): MLSL in its R = 0 regime (mlsl.c:315-317), every COBYLA search
+    eliminating the fixed coordinates (nlopt_optimize_limited -> elimdim).  Its own draw stream: play_mlsl's cases stay as they are"""
+    rng = np.random.default_rng(53000 + draw)
+    n = int(rng.integers(2, 6))
+    alg = GN_MLSL_LDS if rng.random() < 0.5 else GN_MLSL
+    calls = []
+    opt = L.nlopt_create(alg, n)
+    lb, ub = np.full(n, -2.0) - rng.random(n), np.full(n, 2.0) + rng.random(n)
+    fixed = rng.choice(n, int(rng.integers(1, n)), replace=False)
+    x = rng.uniform(lb, ub)
+    for i in fixed:
+        lb[i] = ub[i] = float(rng.choice([x[i], lb[i], 0.0]))
+        x[i] = lb[i]
+    log = [L.nlopt_set_lower_bounds(opt, dp(lb)), L.nlopt_set_upper_bounds(opt, dp(ub))]
+    w = rng.uniform(1, 4, n)
+
+    def f(nn, xp, g, d):
+        xs = np.array([xp[i] for i in range(nn)])
+        calls.append(xs.copy())
+        return float(np.sum(xs ** 2 - np.cos(w * xs)))
+    fcb = FUNC(f)
+    maximise = rng.random() < 0.15
+    log.append((L.nlopt_set_max_objective if maximise else L.nlopt_set_min_objective)(opt, C.cast(fcb, vp), None))
+    log.append(L.nlopt_set_population(opt, int(rng.choice([0, 3, 7, 40]))))
+    if rng.random() < 0.5:
+        log.append(L.nlopt_set_xtol_rel(opt, float(rng.choice([1e-3, 1e-6]))))
+    if rng.random() < 0.3:
+        log.append(L.nlopt_set_initial_step1(opt, float(rng.uniform(0.05, 0.6))))
+    log.append(L.nlopt_set_maxeval(opt, int(rng.choice([5, 60, 300, 900]))))
+    L.nlopt_srand(4321 + draw)
+    minf = C.c_double(0)
+    ret = L.nlopt_optimize(opt, dp(x), C.byref(minf))
+    out = dict(log=log, ret=ret, minf=minf.value, x=x.copy(), nev=L.nlopt_get_numevals(opt), msg=L.nlopt_get_errmsg(opt), calls=np.array(calls),
+               fixed=fixed, lb=lb)
+    L.nlopt_destroy(opt)
+    return out
+
+
+@pytest.mark.parametrize("first", range(0, 40, 20))
+def test_gn_mlsl_with_fixed_coordinates_is_the_references_run_call_by_call(first):
+    R, A = more_bind(O.ref()), more_bind(C.CDLL(EMU))
+    for draw in range(first, first + 20):
+        a, r = play_mlsl_fixed(A, draw), play_mlsl_fixed(R, draw)
+        same(r, a, draw)
+        if a["calls"].size:
+            assert np.all(a["calls"][:, a["fixed"]] == a["lb"][a["fixed"]]), draw      # every call on the fixed coordinates' values
+        if a["ret"] > 0:
+            assert np.all(a["x"][a["fixed"]] == a["lb"][a["fixed"]]), draw

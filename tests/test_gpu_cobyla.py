@@ -27,15 +27,16 @@ def test_gn_mlsl_default_local_optimiser_on_the_device_library_is_the_references
         T.same(T.play_mlsl(R, draw), T.play_mlsl(A, draw), draw)
 
 
-def run_gn_mlsl(lib, alg, obj, n, maxeval, params=(), xtol=1e-5, seed=77, stats=False, population=0):
+def run_gn_mlsl(lib, alg, obj, n, maxeval, params=(), xtol=1e-5, seed=77, stats=False, population=0, lb=None, ub=None, x0=None, maximise=False):
     fptr = nlopt_amd.objective(obj)
     lo, hi = nlopt_amd.objective_box(obj)
     lib.nlopt_set_param.argtypes = [C.c_void_p, C.c_char_p, C.c_double]
     opt = lib.nlopt_create(alg, n)
-    lb, ub = np.full(n, lo), np.full(n, hi)
+    lb = np.full(n, lo) if lb is None else np.array(lb, dtype=np.float64)
+    ub = np.full(n, hi) if ub is None else np.array(ub, dtype=np.float64)
     lib.nlopt_set_lower_bounds(opt, T.dp(lb))
     lib.nlopt_set_upper_bounds(opt, T.dp(ub))
-    lib.nlopt_set_min_objective(opt, C.cast(fptr, C.c_void_p), None)
+    (lib.nlopt_set_max_objective if maximise else lib.nlopt_set_min_objective)(opt, C.cast(fptr, C.c_void_p), None)
     lib.nlopt_set_xtol_rel(opt, xtol)
     lib.nlopt_set_maxeval(opt, maxeval)
     if population:
@@ -44,7 +45,7 @@ def run_gn_mlsl(lib, alg, obj, n, maxeval, params=(), xtol=1e-5, seed=77, stats=
     for k, v in params:
         assert lib.nlopt_set_param(opt, k.encode(), float(v)) > 0
     lib.nlopt_srand(seed)
-    x = np.linspace(0.3 * lo, 0.4 * hi, n)
+    x = np.linspace(0.3 * lo, 0.4 * hi, n) if x0 is None else np.array(x0, dtype=np.float64)
     minf = C.c_double(0)
     ret = lib.nlopt_optimize(opt, T.dp(x), C.byref(minf))
     out = dict(ret=ret, minf=minf.value, x=x.copy(), nevals=lib.nlopt_get_numevals(opt))
@@ -155,6 +156,26 @@ def test_batched_cobyla_kernel_refuses_a_dimension_whose_state_does_not_fit_the_
     assert L.nla_cobyla_fits(51) == 1 and L.nla_cobyla_fits(52) == 0
     with pytest.raises(AssertionError):
         kernel_batch("sphere", 52, np.zeros((1, 52)) + 0.5, np.full(52, -1.0), np.full(52, 1.0), maxeval=10)
+
+
+@pytest.mark.parametrize("n,fixed", [(3, [1]), (8, [0, 5, 7]), (51, list(range(50)))])
+def test_batched_cobyla_kernel_refuses_a_box_with_a_fixed_coordinate(n, fixed):
+    """lb[i] == ub[i]: the reference eliminates the coordinate in front of COBYLA (optimize.c:412-445), the kernel does not — its
+    simplex would have a zero edge there (SIMI = 1/0, ROUNDOFF_LIMITED after a few evaluations).  So it refuses every search of such a
+    box (include/nlopt_amd.h): NLOPT_INVALID_ARGS, no objective call (evaluation count 0, f = HUGE_VAL), the start left as it was.  The
+    same starts in the box without the fixed coordinate run normally"""
+    rng = np.random.default_rng(n)
+    lo, hi = nlopt_amd.objective_box("sphere")
+    lb, ub = np.full(n, lo), np.full(n, hi)
+    starts = rng.uniform(lo, hi, (4, n))
+    for i in fixed:
+        lb[i] = ub[i] = starts[0, i]
+        starts[:, i] = lb[i]
+    a = kernel_batch("sphere", n, starts, lb, ub, maxeval=200)
+    assert a["ret"] == [nlopt_amd.INVALID_ARGS] * 4 and a["nevals"] == [0] * 4, (a["ret"], a["nevals"])
+    assert np.all(a["f"] == np.inf) and np.array_equal(a["x"], starts)
+    free = kernel_batch("sphere", n, starts, np.full(n, lo), np.full(n, hi), maxeval=200)
+    assert all(r > 0 for r in free["ret"]) and all(0 < e <= 200 for e in free["nevals"]), (free["ret"], free["nevals"])
 
 
 @pytest.mark.parametrize("alg,obj,n,maxeval", [(T.GN_MLSL, "sphere", 4, 900), (T.GN_MLSL_LDS, "rosenbrock", 3, 1500), (T.GN_MLSL, "rosenbrock", 6, 3000),

@@ -235,6 +235,35 @@ def test_cobyla_wavefront_kernel_on_lockstep_cpu_threads_is_the_host_algorithm()
     assert r.returncode == 0 and "cobyla emu check: ok" in r.stdout and "DIFFERENT" not in r.stdout, r.stdout + r.stderr
 
 
+@pytest.mark.parametrize("n,fixed", [(4, [1]), (7, [0, 3, 6])])
+def test_emulated_device_cobyla_batch_refuses_a_fixed_coordinate_like_the_kernel(n, fixed):
+    """oracle/emu_device.c's nla_k_cobyla_batch states the kernel's contract (include/nlopt_amd.h): a box with lb[i] == ub[i] is
+    refused — every search NLOPT_INVALID_ARGS, no objective call, the start unchanged — instead of being run through nlopt_optimize,
+    which would eliminate the coordinate and hide a caller that hands such a box to the device (mlsl_driver.c must not)"""
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    path = os.path.join(root, "oracle", "libnlopt_amd_emu.so")
+    if not os.path.exists(path):
+        pytest.skip("no emulated library here")
+    sys.path.insert(0, os.path.join(root, "tools"))
+    try:
+        import cobyla_emu_check as E
+    finally:
+        sys.path.remove(os.path.join(root, "tools"))
+    rng = np.random.default_rng(n)
+    lo, hi = -5.0, 10.0
+    lb, ub = np.full(n, lo), np.full(n, hi)
+    starts = rng.uniform(lo, hi, (3, n))
+    lb[fixed] = ub[fixed] = starts[0, fixed]
+    starts[:, fixed] = lb[fixed]
+    H = C.CDLL(path)
+    a = E.run(H, "rosenbrock", n, starts, lb, ub, maxeval=300)
+    assert a["ret"] == [nlopt_amd.INVALID_ARGS] * 3 and a["nevals"] == [0] * 3, (a["ret"], a["nevals"])
+    assert np.all(a["f"] == np.inf) and np.array_equal(a["x"], starts)
+    free = E.run(H, "rosenbrock", n, starts, np.full(n, lo), np.full(n, hi), maxeval=300)
+    assert all(r > 0 for r in free["ret"]) and all(0 < e <= 300 for e in free["nevals"]), (free["ret"], free["nevals"])
+
+
 def test_ordered_set_and_list_of_worst_rows_against_a_plain_array():
     """crs_driver.c's ordered set (4-ary max-heap, keys in the nodes, batch repair) and the sorted list of worst rows the walk follows
     between two looks at the heap (redrawn beside the device) — the file is #included by tools/ordset_check.c, so these are the product's

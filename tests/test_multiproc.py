@@ -109,6 +109,28 @@ def test_mlsl_driver_over_emulated_device_matches_oracle(world, obj, n, ns, seed
         assert np.array_equal(d["f"][loc], p["floc"]) and np.array_equal(d["accepted"][loc], p["eloc"])
 
 
+@pytest.mark.parametrize("world", [2, 3])
+@pytest.mark.parametrize("obj,n,ns,seed,local,lds,maxeval", [("sphere", 5, 20, 3, "lbfgs", False, 2500), ("rosenbrock", 4, 12, 9, "lbfgs", True, 3000),
+                                                             ("ackley", 6, 10, 5, "mma", False, 2500), ("levy", 4, 16, 7, "mma", True, 1500)])
+def test_mlsl_with_a_fixed_coordinate_over_the_ranks_matches_oracle(world, obj, n, ns, seed, local, lds, maxeval):
+    """MLSL with lb == ub on the last coordinate (MLSL does not eliminate it: R = 0, mlsl.c:315-317, so nearly every ranked point
+    starts a search — many per batch, dealt over the ranks): every rank commits the port's run (pinned to the real reference with
+    a fixed coordinate, test_oracle_pins.py) — samples, local minima and their evaluation counts, result, minimiser bit for bit;
+    the fixed coordinate of the minimiser is its bound exactly"""
+    xs, lo, hi = O.golden_x0(obj, n)
+    lb, ub = np.full(n, lo), np.full(n, hi)
+    lb[n - 1] = ub[n - 1] = 0.5 * (lo + hi) + 0.1                 # (as tests/_mp_worker.py fixes it: fix_last)
+    x0 = np.clip(np.array(xs, dtype=float), lb, ub)
+    a = dict(obj=obj, n=n, pop=ns, seed=seed, maxeval=maxeval, local=local, lds=lds, fix_last=True)
+    p = O.run_port_mlsl(obj, n, ns, seed, maxeval=maxeval, local=local, lds=lds, x0=x0, lb=lb, ub=ub)
+    assert p["x"][n - 1] == lb[n - 1]
+    for d in run_world("gpu_mlsl", a, world=world, extra_env=EMU):
+        _check_against_oracle(d, p)
+        samp, loc = d["kind"] == 3, d["kind"] == 4
+        assert np.array_equal(d["f"][samp], p["fsamp"][:samp.sum()]) and samp.sum() in (len(p["fsamp"]), len(p["fsamp"]) - 1)
+        assert np.array_equal(d["f"][loc], p["floc"]) and np.array_equal(d["accepted"][loc], p["eloc"])
+
+
 @pytest.mark.parametrize("world,first,env", [(1, 0, {}), (1, 15, {"NLA_CRS_UPLOAD": "1", "NLA_CRS_COPY_STATUS": "1"}), (2, 30, {}), (3, 40, {}),
                                              (1, 50, {"NLA_EMU_EVOLVE2": "1"}), (2, 65, {"NLA_EMU_EVOLVE2": "1"})])
 def test_drawn_configurations_of_the_host_drivers_over_the_emulated_device(world, first, env):

@@ -184,6 +184,31 @@ def test_port_mlsl_matches_reference_live(obj, n, ns, seed, kw):
     assert a["minf"] == b["minf"] and np.array_equal(a["x"], b["x"])
 
 
+@need_ref
+@pytest.mark.parametrize("obj,n,ns,seed,fixed,local,lds,kw", [
+    ("sphere", 5, 20, 3, [1], "lbfgs", False, dict(maxeval=2500)),
+    ("rosenbrock", 4, 12, 9, [0, 3], "lbfgs", True, dict(maxeval=3000)),
+    ("ackley", 6, 10, 5, [5], "mma", False, dict(maxeval=2500)),
+    ("levy", 4, 16, 7, [3], "mma", True, dict(maxeval=1500)),
+    ("sphere", 4, 1200, 4, [3], "lbfgs", False, dict(maxeval=2200)),
+])
+def test_port_mlsl_with_a_fixed_coordinate_matches_reference_live(obj, n, ns, seed, fixed, local, lds, kw):
+    """lb[i] == ub[i] under MLSL: the reference does not eliminate it (mlsl.c is not in elimdim_wrapcheck), R_prefactor and with it R
+    are 0 (mlsl.c:315-317), the bound test skips the fixed coordinate (mlsl.c:211-218), LD_LBFGS keeps it as bound type 5 and LD_MMA
+    with sigma = 0.  The port (which the multi-rank MLSL tests lean on) must be the reference's run call by call"""
+    xs, lo, hi = O.golden_x0(obj, n)
+    lb, ub = np.full(n, lo), np.full(n, hi)
+    x0 = np.array(xs, dtype=np.float64)
+    for i in fixed:
+        lb[i] = ub[i] = x0[i]
+    a = O.run_port_mlsl(obj, n, ns, seed, local=local, lds=lds, x0=x0, lb=lb, ub=ub, **kw)
+    b = O.run_ref_mlsl(obj, n, ns, seed, alg=39 if lds else 38, local=local, x0=x0, lb=lb, ub=ub, **kw)
+    assert (a["ret"], a["nevals"]) == (b["ret"], b["nevals"])
+    assert np.array_equal(a["fseq"], b["fseq"]) and np.array_equal(a["xhash"], b["xhash"])
+    assert a["minf"] == b["minf"] and np.array_equal(a["x"], b["x"]) and all(a["x"][i] == lb[i] for i in fixed)
+    assert len(a["floc"]) > 2 * a["iterations"]            # the R = 0 regime: many searches per iteration
+
+
 # ---- LD_MMA without nonlinear constraints, and MLSL with it (GD_MLSL's default local optimiser) ----
 @need_ref
 @pytest.mark.parametrize("obj,n,kw", [

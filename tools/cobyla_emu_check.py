@@ -91,6 +91,18 @@ def main():
         print("%-10s n=%-3d %-8s kernel ret %s nevals %s f %s | host ret %s nevals %s f %s  %s"
               % (obj, n, kind, a["ret"], a["nevals"], a["f"], b["ret"], b["nevals"], b["f"], "IDENTICAL" if same else "DIFFERENT"), flush=True)
         bad += 0 if same else 1
+    # a fixed coordinate (lb == ub): the kernel refuses the box (include/nlopt_amd.h) — INVALID_ARGS, no evaluation, the start unchanged —
+    # where the host algorithm would eliminate the coordinate as the reference does (the contract, not a comparison with the host)
+    for n, fixed in ((4, [1]), (7, [0, 3, 6])):
+        _, lo, hi = O.golden_x0("rosenbrock", n)
+        lov, hiv = np.full(n, float(lo)), np.full(n, float(hi))
+        starts = rng.uniform(lo, hi, (2, n))
+        lov[fixed] = hiv[fixed] = starts[0, fixed]
+        starts[:, fixed] = lov[fixed]
+        a = run(K, "rosenbrock", n, starts, lov, hiv, maxeval=300)
+        ok = a["ret"] == [-2, -2] and a["nevals"] == [0, 0] and np.all(a["f"] == np.inf) and np.array_equal(a["x"], starts)
+        print("rosenbrock n=%-3d fixed %-9s kernel ret %s nevals %s  %s" % (n, fixed, a["ret"], a["nevals"], "REFUSED" if ok else "NOT REFUSED"), flush=True)
+        bad += 0 if ok else 1
     print("cobyla emu check:", "ok" if bad == 0 else "%d case(s) differ" % bad)
     return bad
 
