@@ -602,7 +602,11 @@ int nla_k_esch_fill_rows(int n, int ld, const double *lb, const double *ub, cons
 /* replaces: crossover (esch.c:192-203): offspring id (individual np + id) from words 3 id .. 3 id + 2; slot[i] = row of individual i */
 int nla_k_esch_crossover(int n, int ld, int64_t np, int64_t no, const uint32_t *words, const int32_t *slot, double *R, void *stream);
 /* replaces: the point-mutation loop (esch.c:207-218), `total` steps from the M words W (see hip/esch_kernels.hip); last: no*n ints,
- * scratch: nla_esch_mut_scratch_bytes(M); out (device, 2 x i64): steps the segment holds (< total: too short), words consumed */
+ * scratch: nla_esch_mut_scratch_bytes(M); out (device, 2 x i64): out[0] = complete steps the segment holds, out[1] = words consumed
+ * by the `total` steps, defined only when out[0] >= total.  out[0] < total: the segment was too short; the out[0] complete steps HAVE
+ * been applied, and a second call on the same rows with a longer segment of the same stream leaves the rows as one sufficient call
+ * would have.  A step that leaves its 4096-word block by 64 words or more (some 30 rejected attempts in a row at a block boundary,
+ * probability about 1e-28 per boundary) is outside the contract: the chain breaks there and every M is reported as too short. */
 size_t nla_esch_mut_scratch_bytes(int64_t M);
 int nla_k_esch_mutate(const uint32_t *W, int64_t M, int64_t total, int n, int ld, int64_t np, int64_t no, const double *lb,
                       const double *ub, const int32_t *slot, double *R, int32_t *last, void *scratch, int64_t *out, void *stream);

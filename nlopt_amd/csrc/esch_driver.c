@@ -242,8 +242,10 @@ nlopt_result nla_esch_minimize(nlopt_opt opt, int n, nlopt_func f, void *f_data,
                                   D.d_out, D.st) ||
                 nla_memcpy_d2h(out, D.d_out, sizeof out, D.st) || nla_stream_sync(D.st)) { snprintf(D.err, sizeof D.err, "mutation pass failed"); DEVFAIL(); }
             if (out[0] >= total) break;
-            /* the segment ended before the last step did: nothing beyond the first out[0] steps was applied wrongly — later
-             * steps only overwrite; redo the whole pass on a longer segment (rows touched so far get the same values again) */
+            /* the segment ended before the last step did (out[0] < total; out[1] is then undefined): the out[0] complete steps HAVE
+             * been applied.  Redo the whole pass on a longer segment of the same stream: it writes every element those steps wrote
+             * again, its last step on an element last, so the rows end as one sufficient pass would have left them
+             * (tests/test_gpu_esch_kernels.py::test_mutate_exact_fit_too_short_and_retried) */
             if (tries >= 6) { snprintf(D.err, sizeof D.err, "mutation chain did not fit the stream segment"); DEVFAIL(); }
             M *= 2;
         }

@@ -327,8 +327,12 @@ extern "C" size_t nla_esch_mut_scratch_bytes(int64_t M)
 }
 
 /* the (no n)/10 point mutations of one generation from the M stream words W; last: no*n ints of scratch (zeroed here);
- * h-visible result through `out` (device, 2 x int64): out[0] = steps the segment holds (< total: M was too short, nothing
- * was applied), out[1] = words consumed by the `total` steps */
+ * h-visible result through `out` (device, 2 x int64): out[0] = complete steps the segment holds, out[1] = words consumed by the
+ * `total` steps — defined only when out[0] >= total.  out[0] < total: M was too short; the out[0] complete steps HAVE been applied
+ * (with "last step wins" among them), and a second call on the same rows with a longer segment of the same stream leaves the rows as
+ * one sufficient call would have: its steps write every element again, the last of them last (tests/test_gpu_esch_kernels.py).
+ * A step that leaves its block by ESCH_ENTRIES (64) words or more — some 30 rejected attempts in a row at a block boundary,
+ * probability about 1e-28 per boundary — breaks the chain there: the launcher then reports "too short" for every M. */
 extern "C" int nla_k_esch_mutate(const uint32_t *W, int64_t M, int64_t total, int n, int ld, int64_t np, int64_t no, const double *lb,
                                  const double *ub, const int32_t *slot, double *R, int32_t *last, void *scratch, int64_t *out, void *stream)
 {

@@ -689,7 +689,7 @@ int nla_k_isres_eval(int obj, int n, int ld, const double *X, int64_t pop, int m
         const double *x = X + (size_t) k * (size_t) ld;
         double pen = 0, gpen = 0;
         int feas = 1;
-        F[k] = sign * nla_obj_eval_seq(obj, (unsigned) n, x, NULL);
+        if (obj >= 0) F[k] = sign * nla_obj_eval_seq(obj, (unsigned) n, x, NULL);      /* obj < 0: the constraint part only, F untouched */
         for (int c = 0; c < m + p; ++c) {
             double g = nla_con_blocksum_seq((unsigned) n, x, NULL, con[c].q, con[c].Q);
             if (c == m) gpen = pen;
