@@ -209,6 +209,10 @@ def lib():
     L.nla_k_isres_inverse.argtypes = [C.c_int64, vp, vp, vp]
     L.nla_k_isres_evolve_rounds.argtypes = ([C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_double, C.c_double] + [vp] * 12 +
                                             [C.c_int, vp])   # ..., lb, ub, z, irank, inv, X, S, x0c, state, rho, ws, rounds, stream
+    L.nla_k_isres_evolve.argtypes = ([C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_double, C.c_double] +
+                                     [vp] * 9)   # ..., lb, ub, z, irank, X, S, scratch, state, stream
+    L.nla_k_isres_evolve_parent_mu.argtypes = [C.c_int, C.c_int, C.c_int64] + [vp] * 7   # ..., lb, ub, irank, X, S, mu_rp, stream
+    L.nla_isres_evolve2_supported.argtypes = [C.c_int]
     L.nla_k_crs_commit.argtypes = [C.c_int, C.c_int, vp, vp, vp, C.c_int, vp, vp, vp, vp]
     L.nla_k_crs_mutate.argtypes = [C.c_int, vp, vp, vp, vp, vp, vp]
     L.nla_mt_jump_poly_words.argtypes = [C.c_uint64, vp]

@@ -364,6 +364,10 @@ __global__ __launch_bounds__(64) void isres_evolve_kernel(isres_evolve_args A)
         const volatile double *sp = A.phase == 0 ? Sv + (size_t) ri * ld : sown;
         const volatile double *xk1 = Xv + (size_t) (k + 1) * ld;    /* physical row k+1 (variation only) */
         const bool self = (k + 1 == rk);
+        /* a child whose deviates run out must not be written at all: the mutation phase, which has no use for the copies of the own rows,
+         * collects the child there and copies it once the fix-point has settled (every lane its own chunk) */
+        volatile double *xout = A.phase == 0 ? xown : Xv + (size_t) rk * ld;
+        volatile double *sout = A.phase == 0 ? sown : Sv + (size_t) rk * ld;
         int64_t shift = 0;                  /* deviates consumed by the chunks before this lane's */
         int64_t total = 0;
         for (int round = 0; round < 66; ++round) {
@@ -397,10 +401,9 @@ __global__ __launch_bounds__(64) void isres_evolve_kernel(isres_evolve_args A)
                     snew = sigi + ALPHA * (sg - sigi);
                     cur += 1 + t; used += 1 + t;
                 }
-                Xv[(size_t) rk * ld + j] = xnew;
-                Sv[(size_t) rk * ld + j] = snew;
+                xout[j] = xnew;
+                sout[j] = snew;
             }
-            if (__ballot(over)) { ranout = true; break; }
             /* exclusive prefix sum of `used` over the lanes */
             int64_t incl = used;
             for (int off = 1; off < 64; off <<= 1) {
@@ -411,7 +414,15 @@ __global__ __launch_bounds__(64) void isres_evolve_kernel(isres_evolve_args A)
             total = __shfl(incl, 63, 64);
             const bool changed = nshift != shift;
             shift = nshift;
-            if (!__ballot(changed)) break;
+            /* a lane that met the end of the deviates says so only for the start it assumed: they have run out iff the first such lane and
+             * every lane before it started where this round's prefix sums put them (lane l does from round l on) */
+            const unsigned long long overm = __ballot(over), chm = __ballot(changed);
+            if (overm) {
+                const int first = __ffsll((long long) overm) - 1;
+                if (!(chm & ((2ull << first) - 1ull))) { ranout = true; break; }
+                continue;
+            }
+            if (!chm) break;
         }
         if (ranout) {
             if (A.phase == 1) {             /* undo the partial in-place update */
@@ -420,6 +431,8 @@ __global__ __launch_bounds__(64) void isres_evolve_kernel(isres_evolve_args A)
             }
             break;
         }
+        if (A.phase == 0)
+            for (int j = j0; j < j1; ++j) { Xv[(size_t) rk * ld + j] = xout[j]; Sv[(size_t) rk * ld + j] = sout[j]; }
         pos += 1 + total;
         __threadfence();
     }
@@ -458,7 +471,7 @@ __device__ __forceinline__ int ev_block_exscan(int v, int *s_w, int &total)
 __global__ __launch_bounds__(EV_T) void isres_evolve_lds_kernel(isres_evolve_args A)
 {
     extern __shared__ double sm[];
-    __shared__ int s_w[EV_T / 64];
+    __shared__ int s_w[EV_T / 64], s_first;      /* s_first: the first thread of a fix-point round that met the end of the deviates */
     __shared__ int8_t s_tab[2][EV_T][EV_D];     /* per-thread shift maps of the one-pass path, ping-pong */
     const int tid = threadIdx.x;
     const int n = A.n, ld = A.ld;
@@ -480,6 +493,7 @@ __global__ __launch_bounds__(EV_T) void isres_evolve_lds_kernel(isres_evolve_arg
         for (int j = tid; j < n; j += EV_T) x0c[j] = __builtin_nontemporal_load(A.scratch + j);
     }
     __syncthreads();
+    if (tid == 0) s_first = EV_T;
     bool ranout = false;
     int64_t rounds_total = 0;
     int64_t c_eval = 0, c_scan = 0, c_fin = 0, c_all = 0, c_stage = 0;
@@ -629,12 +643,21 @@ __global__ __launch_bounds__(EV_T) void isres_evolve_lds_kernel(isres_evolve_arg
                 so[j] = snew;
             }
             const int nshift = ev_block_exscan(used, s_w, total);
-            const int flags = (over ? 2 : 0) | (nshift != shift ? 1 : 0);
+            const bool changed = nshift != shift;
             shift = nshift;
             ++rounds_total;
-            const int any = __syncthreads_or(flags);
-            if (any & 2) { ranout = true; break; }
-            if (!(any & 1)) break;
+            /* A thread that met the end of the deviates says so only for the start it assumed: the deviates have run out iff the FIRST such
+             * thread and every thread before it started where the prefix sums of this round put them (by induction thread t does from
+             * round t on); otherwise the fix-point goes on.  (__syncthreads_or tells whether ANY thread's predicate is set, not which
+             * bits: one reduction per round, a second only in a round in which some thread met the end.) */
+            if (over) atomicMin(&s_first, tid);
+            if (!__syncthreads_or(over || changed)) break;
+            const int first = s_first;
+            if (first < EV_T) {
+                const int unsettled = __syncthreads_or(changed && tid <= first);
+                if (tid == 0) s_first = EV_T;       /* (read by everybody before the reduction above, next written after the scan's barriers) */
+                if (!unsettled) { ranout = true; break; }
+            }
         }
         if (ranout) break;                  /* nothing of this individual has been written */
         {

@@ -887,7 +887,8 @@ int nla_k_isres_evolve_rounds(int n, int ld, int phase, int64_t pop, int64_t sur
 {
     EMU_LAUNCH();
     const int64_t kend = phase == 0 ? pop : survivors;
-    (void) inv; (void) rho; (void) ws; (void) mu_rp;
+    (void) inv; (void) rho; (void) ws;
+    if (n < 1 || n > 1150 || (phase == 0 && !mu_rp)) return EMU_ERR;            /* the launcher's refusals: nothing is touched */
     for (int r = 0; r < rounds; ++r) {
         int64_t first = state[0], limit, stop = first + 256 < kend ? first + 256 : kend;
         int rc;
