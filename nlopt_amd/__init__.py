@@ -215,6 +215,28 @@ def lib():
     L.nla_isres_evolve2_supported.argtypes = [C.c_int]
     L.nla_k_crs_commit.argtypes = [C.c_int, C.c_int, vp, vp, vp, C.c_int, vp, vp, vp, vp]
     L.nla_k_crs_mutate.argtypes = [C.c_int, vp, vp, vp, vp, vp, vp]
+    # the launchers crs_engine.c uses on its usual path: lists as kernel arguments (host arrays), the fused commit, the doorbell,
+    # the production form of the window launch, the column-sharded pass
+    L.nla_host_malloc.argtypes = [C.c_size_t]
+    L.nla_host_malloc.restype = vp
+    L.nla_host_free.argtypes = [vp]
+    L.nla_host_free.restype = None
+    L.nla_k_crs_advance_args.argtypes = L.nla_k_crs_advance.argtypes
+    L.nla_k_crs_advance_cols.argtypes = [C.c_int] + L.nla_k_crs_advance.argtypes           # n, ncol, ld, ...
+    L.nla_k_crs_advance_commit_args.argtypes = ([C.c_int, C.c_int, vp, C.c_int64, vp, vp, vp, C.c_uint32, C.c_uint64, C.c_int, vp, C.c_int,
+                                                 vp, vp, C.c_int, vp, vp, vp] +
+                                                [vp, C.c_int, vp, vp, vp, C.c_int, vp])   # ..., TX, TM, ncommit, h_slot, h_kind, h_row, variant, stream
+    L.nla_k_crs_finish_args.argtypes = L.nla_k_crs_finish.argtypes
+    L.nla_k_crs_finish_args_bell.argtypes = L.nla_k_crs_finish.argtypes[:-1] + [vp, vp, C.c_uint32, vp]   # ..., status, bell_count, bell, bell_seq, stream
+    L.nla_k_crs_commit_args.argtypes = L.nla_k_crs_commit.argtypes
+    L.nla_k_crs_commit_zero.argtypes = L.nla_k_crs_commit.argtypes[:-1] + [C.c_int, vp, C.c_size_t, vp]   # ..., row, lists_on_host, zero, zero_bytes, stream
+    L.nla_k_crs_chain_lean.argtypes = L.nla_k_crs_chain.argtypes[:-1] + [C.c_int, vp]                      # ..., fwcap, ctrl_is_zero, stream
+    L.nla_k_crs_sh_init_rows.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int64, C.c_int64, vp, vp]
+    L.nla_k_crs_sh_mutate_pack.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int64, vp, vp, vp, C.c_uint32, C.c_uint64, C.c_int,
+                                           vp, vp, C.c_int, vp, vp, vp, C.c_int, C.c_int, vp]
+    L.nla_k_crs_sh_eval.argtypes = [C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_int, vp, vp, C.c_int, vp, C.c_int, vp, vp, vp, vp]
+    L.nla_k_crs_commit_sh.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp, vp, vp, vp, C.c_size_t,
+                                      C.c_int, C.c_int, C.c_int, vp, vp]
     L.nla_mt_jump_poly_words.argtypes = [C.c_uint64, vp]
     L.nla_mt_jump_poly_words.restype = None
     L.nla_mt_jump_poly_pow2.argtypes = [C.c_int]

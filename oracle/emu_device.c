@@ -225,6 +225,7 @@ int nla_k_crs_commit_sh(int nc, int ld, int ldf, int c0, double *X, const double
                         int n, int best_slot, int best_kind, double *xbest, void *stream)
 {
     (void) stream;
+    if (ncommit < 0 || ncommit > 128 || (zero_bytes & 3u)) return EMU_ERR;
     EMU_LAUNCH();
     if (zero && zero_bytes) memset(zero, 0, zero_bytes);
     if (best_slot >= 0) memcpy(xbest, (best_kind == 1 ? TX : TM) + (size_t) best_slot * (size_t) ldf, sizeof(double) * (size_t) n);
@@ -947,6 +948,7 @@ int nla_k_crs_advance_args(int n, int ld, const double *X, int64_t i0, const int
                            const int32_t *last_ring, uint32_t ring_blocks, uint64_t first_block, int K, const int64_t *h_W, int nW,
                            const int32_t *h_t_in, int32_t *t_out, int slot_mask, const double *lb, const double *ub, double *TX, int variant, void *st)
 {
+    if (K > 128 || nW > 128) return EMU_ERR;                               /* the lists are kernel arguments on the device: 128 entries */
     EMU_LAUNCH();
     return nla_k_crs_advance(n, ld, X, i0, jn_ring, pos_ring, last_ring, ring_blocks, first_block, K, h_W, nW, h_t_in, t_out, slot_mask, lb, ub, TX, variant, st);
 }
@@ -956,6 +958,7 @@ int nla_k_crs_advance_cols(int n, int ncol, int ld, const double *X, int64_t i0,
                            const int32_t *last_ring, uint32_t ring_blocks, uint64_t first_block, int K, const int64_t *W, int nW, const int32_t *t_in,
                            int32_t *t_out, int slot_mask, const double *lb, const double *ub, double *TX, int variant, void *st)
 {
+    if (ncol < 1 || ncol > ld) return EMU_ERR;
     EMU_LAUNCH();
     (void) variant; (void) st;
     for (int a = 0; a < K; ++a) {
@@ -1017,7 +1020,7 @@ int nla_k_crs_sh_eval(int obj, int n, int colper, uint64_t first_block, int K, c
     const double sign = emu_obj_sign(&obj);
     double *p;
     (void) st;
-    if (obj < 0 || obj >= NLA_OBJ_COUNT || colper < 1) return EMU_ERR;
+    if (obj < 0 || obj >= NLA_OBJ_COUNT || colper < 1 || world < 1) return EMU_ERR;
     p = (double *) malloc(sizeof(double) * (size_t) (n > 0 ? n : 1));
     for (int a = 0; a < K; ++a) {
         const int q = (int) ((first_block + (uint64_t) a) & (uint64_t) slot_mask);
@@ -1052,7 +1055,10 @@ void orc_k_crs_chain(int obj, int n, int ld, const double *X, int64_t i0, double
                      const int32_t *last_ring, const uint32_t *words_ring, uint32_t ring_blocks, uint64_t first_block, int K,
                      const int64_t *W, const double *Wf, int nW, int slot_mask, const double *lb, const double *ub, double *TX, double *TM,
                      orc_slot_status *status, uint32_t *fwcnt, uint32_t *fwrec, int fwcap, const orc_slot_status *decide_with, uint32_t *dbg);
-size_t nla_crs_chain_ctrl_bytes(int K, int nW) { (void) K; (void) nW; return 64; }
+/* the device's layout (hip/crs_chain.hip): 8 words (ticket, lock, next, halt, naccept, wp, nextra, pk), 32 f64 + 32 i64 of landed values,
+ * 2K f64, done[K], K unused words, rowstate[nW], 8 words.  The emulation fills in what a caller may read back: next, wp, nextra and
+ * rowstate as the sequential statement leaves them; halt stays 0 — every slot of the window is computed here, which the contract allows */
+size_t nla_crs_chain_ctrl_bytes(int K, int nW) { return 32 + 512 + 16 * (size_t) K + 4 * (2 * (size_t) K + (size_t) nW + 8); }
 int nla_crs_chain_chunks(int n, int ld) { (void) ld; return (n + 63) / 64; }
 int nla_k_crs_chain(int obj, int n, int ld, const double *X, int64_t i0, double f_best, const int32_t *jn_ring, const int32_t *pos_ring,
                     const int32_t *last_ring, const uint32_t *words_ring, uint32_t ring_blocks, uint64_t first_block, int K, const int64_t *W,
@@ -1060,10 +1066,20 @@ int nla_k_crs_chain(int obj, int n, int ld, const double *X, int64_t i0, double 
                     uint32_t ticket_base, nla_crs_slot_status *status, uint32_t *fwcnt, uint32_t *fwrec, int fwcap, void *st)
 {
     EMU_LAUNCH();
-    (void) w_on_host; (void) ctrl; (void) ticket_base; (void) st;
-    if (K > 256 || nW > 256 || obj < 0) return EMU_ERR;
-    orc_k_crs_chain(obj, n, ld, X, i0, f_best, jn_ring, pos_ring, last_ring, words_ring, ring_blocks, first_block, K, W, Wf, nW, slot_mask, lb, ub,
-                    TX, TM, (orc_slot_status *) status, fwcnt, fwrec, fwcap, NULL, NULL);
+    (void) ticket_base; (void) st;
+    if (K > 256 || nW > 256 || nW < 0 || obj < 0 || (w_on_host && nW > 128)) return EMU_ERR;
+    if (K <= 0) return 0;
+    {
+        uint32_t *dbg = (uint32_t *) calloc((size_t) (8 + nW), sizeof(uint32_t)), *c = (uint32_t *) ctrl;
+        if (!dbg) return EMU_ERR;
+        orc_k_crs_chain(obj, n, ld, X, i0, f_best, jn_ring, pos_ring, last_ring, words_ring, ring_blocks, first_block, K, W, Wf, nW, slot_mask, lb, ub,
+                        TX, TM, (orc_slot_status *) status, fwcnt, fwrec, fwcap, NULL, dbg);
+        if (c) {
+            c[2] = dbg[0]; c[3] = 0; c[5] = dbg[2]; c[6] = dbg[3];
+            memcpy((char *) ctrl + 32 + 512 + 24 * (size_t) K, dbg + 8, sizeof(uint32_t) * (size_t) nW);
+        }
+        free(dbg);
+    }
     return 0;
 }
 int nla_k_crs_chain_lean(int obj, int n, int ld, const double *X, int64_t i0, double f_best, const int32_t *jn_ring, const int32_t *pos_ring,
@@ -1096,7 +1112,9 @@ int nla_k_crs_finish(int obj, int n, int ld, const double *X, int64_t i0, const 
                 orc_k_mutate(n, X + (size_t) i0 * (size_t) ld, x, words_ring + (size_t) ((block + 1) % ring_blocks) * 2 * (size_t) n, lb, ub, m);
                 fM = fM_ring[q] = sign * nla_obj_eval_seq(obj, (unsigned) n, m, NULL);                /* crs.c:139-146 */
             } else if (t1 == n) { fT = fT_ring[q]; fM = fM_ring[q]; }
-        }
+        } else if (obj == -2 && newly)              /* the mutation only: the objective is a user-supplied kernel the caller runs afterwards */
+            orc_k_mutate(n, X + (size_t) i0 * (size_t) ld, x, words_ring + (size_t) ((block + 1) % ring_blocks) * 2 * (size_t) n, lb, ub,
+                         TM + (size_t) q * (size_t) ld);
         status[a].fT = fT; status[a].fM = fM; status[a].t = t1; status[a].pad = 0;
     }
     return 0;
@@ -1105,6 +1123,7 @@ int nla_k_crs_finish_args(int obj, int n, int ld, const double *X, int64_t i0, c
                           uint32_t ring_blocks, uint64_t first_block, int K, const int32_t *h_t_in, const int32_t *t_out, int slot_mask,
                           const double *lb, const double *ub, double *fT_ring, double *fM_ring, nla_crs_slot_status *status, void *st)
 {
+    if (K > 128) return EMU_ERR;
     EMU_LAUNCH();
     return nla_k_crs_finish(obj, n, ld, X, i0, TX, TM, words_ring, ring_blocks, first_block, K, h_t_in, t_out, slot_mask, lb, ub, fT_ring, fM_ring, status, st);
 }
@@ -1113,6 +1132,7 @@ int nla_k_crs_finish_args_bell(int obj, int n, int ld, const double *X, int64_t 
                                const double *lb, const double *ub, double *fT_ring, double *fM_ring, nla_crs_slot_status *status,
                                uint32_t *bell_count, uint32_t *bell, uint32_t bell_seq, void *st)
 {
+    if (K > 128 || !bell_count || !bell) return EMU_ERR;
     const int rc = nla_k_crs_finish_args(obj, n, ld, X, i0, TX, TM, words_ring, ring_blocks, first_block, K, h_t_in, t_out, slot_mask, lb, ub,
                                          fT_ring, fM_ring, status, st);
     (void) bell_count;
@@ -1138,6 +1158,7 @@ int nla_k_crs_commit_zero(int n, int ld, double *X, const double *TX, const doub
 int nla_k_crs_commit_args(int n, int ld, double *X, const double *TX, const double *TM, int ncommit, const int32_t *h_slot, const int32_t *h_kind,
                           const int64_t *h_row, void *st)
 {
+    if (ncommit > 128) return EMU_ERR;
     EMU_LAUNCH();
     return nla_k_crs_commit(n, ld, X, TX, TM, ncommit, h_slot, h_kind, h_row, st);
 }
@@ -1147,7 +1168,9 @@ int nla_k_crs_advance_commit_args(int n, int ld, double *X, int64_t i0, const in
                                   const int32_t *h_slot, const int32_t *h_kind, const int64_t *h_row, int variant, void *st)
 {
     /* (one launch on the device, with the rows' reads forwarded; here simply one after the other: the same values) */
-    int rc = nla_k_crs_commit_args(n, ld, X, TX, TM, ncommit, h_slot, h_kind, h_row, st);
+    int rc;
+    if (K > 128 || nW > 128 || ncommit > 16 || ncommit < 0) return EMU_ERR;
+    rc = nla_k_crs_commit_args(n, ld, X, TX, TM, ncommit, h_slot, h_kind, h_row, st);
     if (rc) return rc;
     return nla_k_crs_advance_args(n, ld, X, i0, jn_ring, pos_ring, last_ring, ring_blocks, first_block, K, h_W, nW, h_t_in, t_out, slot_mask, lb, ub,
                                   TX, variant, st);

@@ -177,7 +177,7 @@ def test_chain_kernel_resolves_the_window_like_the_sequential_statement(L, obj, 
     chain_kernel_case(L, obj, n, N, K, i0)
 
 
-def chain_kernel_case(L, obj, n, N, K, i0):
+def chain_kernel_case(L, obj, n, N, K, i0, lean=None):
     """nla_k_crs_chain (hip/crs_chain.hip): one launch computes every slot of the window, evaluates it, replays the accept / reject
     chain on the window's worst rows and lets later slots read what the chain says a worst row holds at their turn.  Against the
     sequential statement orc_k_crs_chain: bit-exact trial points and mutations, f within 1e-10, the same records of what every
@@ -185,13 +185,31 @@ def chain_kernel_case(L, obj, n, N, K, i0):
     the in-kernel waiting, evaluation and resolution are what is tested.  The objective values of the rows are random, so the
     chain has rejections, accepted mutations and values landing among the worst rows again.  The chain is advanced by the launch's
     resolver wavefront (hip/crs_chain_resolver.h); a trial that becomes the new best point ends the window (control word `halt` =
-    2 | (slot + 1) << 8): later slots may come back "not computed" (status.t = 0), never with a wrong point."""
+    2 | (slot + 1) << 8): later slots may come back "not computed" (status.t = 0), never with a wrong point.
+    lean = "host" / "dev": the launch as crs_engine.c issues it (tests/test_gpu_crs_launchers.py) — nla_k_crs_commit_zero in front
+    (two accepted points of an earlier window into their rows, commit lists as host / device arrays, and the control block cleared
+    behind its ticket word), then nla_k_crs_chain_lean with ctrl_is_zero = 1, W / Wf as host arrays, status / fwcnt / fwrec in pinned
+    host memory.  The clearing is asserted BEFORE the window is launched."""
     P = O.port()
     ring = 2 * K + 3
     first = 3 * ring + 2
     mask = 511
     ld, lb, ub, X, w0, jn0, pos0, last0 = _spec_inputs(n, N, ring, 177 + n, obj, align=16)      # the chain kernel's contract: rows on 128-byte lines
     oid = O.OBJ[obj]
+    nslot = mask + 1
+    TX0, TM0 = np.zeros((nslot, ld)), np.zeros((nslot, ld))
+    X0 = X.copy() if lean else X                # the population as the device holds it before the launch
+    if lean:
+        # two points accepted in an earlier window wait in slots outside this one's; X (the statement's population) holds them already
+        c_slot = np.array([(first + K + 5) & mask, (first + K + 9) & mask], np.int32)
+        c_kind = np.array([1, 2], np.int32)
+        c_row = np.array([(i0 + 1) % N, (i0 + 2) % N], np.int64)
+        assert not set(c_slot.tolist()) & {(first + a) & mask for a in range(K)} and nslot > K + 9
+        crng = np.random.default_rng(900 + n)
+        for s_, k_, r_ in zip(c_slot, c_kind, c_row):
+            (TX0 if k_ == 1 else TM0)[s_, :n] = crng.uniform(lb, ub)
+            X[r_, :n] = (TX0 if k_ == 1 else TM0)[s_, :n]
+        assert not np.array_equal(X, X0)
     ent = [(first + a) % ring for a in range(ring)]
     w = np.zeros(2 * n * ring, np.uint32)
     jn, pos, last = np.zeros(ring, np.int32), np.zeros(ring * n, np.int32), np.zeros(ring, np.int32)
@@ -214,25 +232,56 @@ def chain_kernel_case(L, obj, n, N, K, i0):
     class St(C.Structure):
         _fields_ = [("fT", C.c_double), ("fM", C.c_double), ("t", C.c_int32), ("pad", C.c_int32)]
     fwcap = 48
-    nslot = mask + 1
     P.orc_k_crs_chain.restype = None
     P.orc_k_crs_chain.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_uint32, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-    dX, dlb, dub, dw = DevBuf.from_array(X), DevBuf.from_array(lb), DevBuf.from_array(ub), DevBuf.from_array(w)
+    dX, dlb, dub, dw = DevBuf.from_array(X0), DevBuf.from_array(lb), DevBuf.from_array(ub), DevBuf.from_array(w)
     dj, dp, dl = DevBuf.from_array(jn), DevBuf.from_array(pos), DevBuf.from_array(last)
     dW, dWf = DevBuf.from_array(W), DevBuf.from_array(Wf)
-    dTX, dTM = DevBuf.from_array(np.zeros(nslot * ld), uncached=True), DevBuf.from_array(np.zeros(nslot * ld), uncached=True)
+    dTX, dTM = DevBuf.from_array(TX0, uncached=True), DevBuf.from_array(TM0, uncached=True)
     cb = L.nla_crs_chain_ctrl_bytes(256, 256)
     dctrl = DevBuf.from_array(np.zeros(cb, np.uint8), uncached=True)      # the kernel's contract: TX, TM, ctrl are uncached memory
     dst = DevBuf(C.sizeof(St) * K)
     dcnt, drec = DevBuf.from_array(np.zeros(K, np.uint32)), DevBuf.from_array(np.zeros(K * fwcap, np.uint32))
+    if lean:
+        assert nW <= 128
+        cbz = L.nla_crs_chain_ctrl_bytes(K, nW)                          # what the engine clears: this window's block, not the allocation
+        assert 4 < cbz < cb - 64 and cbz % 4 == 0
+        dcs, dck, dcr = DevBuf.from_array(c_slot), DevBuf.from_array(c_kind), DevBuf.from_array(c_row)
+        hbytes = C.sizeof(St) * K + 4 * K + 4 * K * fwcap
+        hmem = L.nla_host_malloc(hbytes)
+        assert hmem
+        h_st, h_cnt, h_rec = hmem, hmem + C.sizeof(St) * K, hmem + C.sizeof(St) * K + 4 * K
+        dirty = np.full(cb, 0xA5, np.uint8)
+        dirty[:4] = 0                                                   # the ticket word: zero before the first launch
+        assert L.nla_memcpy_h2d(dctrl.ptr, dirty.ctypes.data, cb, None) == 0 and L.nla_stream_sync(None) == 0
+    worst = 0.0                                 # largest relative difference in f (returned: the caller may report it)
     for rep in range(2):                        # twice on the same control block: the ticket base carries over
-        assert L.nla_memset(dst.ptr, 0, C.sizeof(St) * K, None) == 0
-        assert L.nla_k_crs_chain(oid, n, ld, dX.ptr, i0, fbest, dj.ptr, dp.ptr, dl.ptr, dw.ptr, ring, first, K, dW.ptr, dWf.ptr, nW, 0, mask,
-                                 dlb.ptr, dub.ptr, dTX.ptr, dTM.ptr, dctrl.ptr, rep * L.nla_crs_chain_tickets(n, ld, K), dst.ptr, dcnt.ptr,
-                                 drec.ptr, fwcap, None) == 0
-        assert L.nla_stream_sync(None) == 0
+        if lean:
+            before = dctrl.to_array(np.uint8, cb)
+            assert before[4:cbz].any()                                  # (the second repetition's block is dirty from the first window)
+            lists = (c_slot.ctypes.data, c_kind.ctypes.data, c_row.ctypes.data) if lean == "host" else (dcs.ptr, dck.ptr, dcr.ptr)
+            assert L.nla_k_crs_commit_zero(n, ld, dX.ptr, dTX.ptr, dTM.ptr, len(c_row), lists[0], lists[1], lists[2], 1 if lean == "host" else 0,
+                                           dctrl.ptr + 4, cbz - 4, None) == 0
+            assert L.nla_stream_sync(None) == 0
+            after = dctrl.to_array(np.uint8, cb)
+            assert not after[4:cbz].any(), ("words left uncleared", np.flatnonzero(after[4:cbz])[:8].tolist())
+            assert np.array_equal(after[:4], before[:4]) and np.array_equal(after[cbz:], before[cbz:])     # ticket word, bytes behind the block
+            assert np.array_equal(dX.to_array(np.float64, N * ld).reshape(N, ld), X)                       # the committed rows, no other
+            C.memset(hmem, 0, hbytes)
+            assert L.nla_k_crs_chain_lean(oid, n, ld, dX.ptr, i0, fbest, dj.ptr, dp.ptr, dl.ptr, dw.ptr, ring, first, K, W.ctypes.data,
+                                          Wf.ctypes.data, nW, 1, mask, dlb.ptr, dub.ptr, dTX.ptr, dTM.ptr, dctrl.ptr,
+                                          rep * L.nla_crs_chain_tickets(n, ld, K), h_st, h_cnt, h_rec, fwcap, 1, None) == 0
+            assert L.nla_stream_sync(None) == 0
+            assert L.nla_memcpy_h2d(dst.ptr, h_st, C.sizeof(St) * K, None) == 0 and L.nla_memcpy_h2d(dcnt.ptr, h_cnt, 4 * K, None) == 0
+            assert L.nla_memcpy_h2d(drec.ptr, h_rec, 4 * K * fwcap, None) == 0 and L.nla_stream_sync(None) == 0
+        else:
+            assert L.nla_memset(dst.ptr, 0, C.sizeof(St) * K, None) == 0
+            assert L.nla_k_crs_chain(oid, n, ld, dX.ptr, i0, fbest, dj.ptr, dp.ptr, dl.ptr, dw.ptr, ring, first, K, dW.ptr, dWf.ptr, nW, 0, mask,
+                                     dlb.ptr, dub.ptr, dTX.ptr, dTM.ptr, dctrl.ptr, rep * L.nla_crs_chain_tickets(n, ld, K), dst.ptr, dcnt.ptr,
+                                     drec.ptr, fwcap, None) == 0
+            assert L.nla_stream_sync(None) == 0
         raw = dst.to_array(np.uint8, C.sizeof(St) * K)
         st = np.frombuffer(raw.tobytes(), dtype=[("fT", "f8"), ("fM", "f8"), ("t", "i4"), ("pad", "i4")])
         craw = dctrl.to_array(np.uint8, cb)
@@ -245,7 +294,7 @@ def chain_kernel_case(L, obj, n, N, K, i0):
         # last bits; with N barely above n the trial points are nearly equal and so are their f: a comparison could go either way)
         dev_status = (St * K)()
         C.memmove(dev_status, raw.tobytes(), C.sizeof(St) * K)
-        TXr, TMr = np.zeros((nslot, ld)), np.zeros((nslot, ld))
+        TXr, TMr = TX0.copy(), TM0.copy()
         str_ = (St * K)()
         cntr, recr = np.zeros(K, np.uint32), np.zeros(K * fwcap, np.uint32)
         dbg = np.zeros(8 + 256, np.uint32)
@@ -275,8 +324,16 @@ def chain_kernel_case(L, obj, n, N, K, i0):
             assert np.array_equal(TX[qa, :n], TXr[qa, :n]), a
             assert np.array_equal(TM[qa, :n], TMr[qa, :n]), a
         assert close(st["fT"][done], fTr[done], scale) and close(st["fM"][done], fMr[done], scale)
+        for got, want in ((st["fT"][done], fTr[done]), (st["fM"][done], fMr[done])):
+            if want.size:
+                worst = max(worst, float(np.max(np.abs(got - want) / np.maximum(np.abs(want), scale))))
+        if lean:                                # the window left the slots the commits came from alone
+            assert np.array_equal(TX[c_slot], TX0[c_slot]) and np.array_equal(TM[c_slot], TM0[c_slot])
+    if lean:
+        L.nla_host_free(hmem)
     kinds = (recr >> 16) & 3
     assert K < 8 or (cntr.sum() > 0 and (kinds[recr > 0] > 0).any())      # the case does exercise reading from producers
+    return worst
 
 
 @pytest.mark.parametrize("obj,n,N,K,i0,variant", [("rastrigin", 10, 100, 7, 0, 0), ("rastrigin", 10, 11, 5, 10, 0),

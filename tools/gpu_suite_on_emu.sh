@@ -3,7 +3,7 @@
 # (tests/_emu_plugin.py -> oracle/libnlopt_amd_emu.so).  Everything the GPU suite asserts about drivers, dispatcher, collectives and
 # error paths is checked against the same oracle; the HIP kernels are NOT (the emulation replaces them).  Left out: what needs the
 # real device or the real library file — the reference's client programs and CLI linked against libnlopt_amd.so, user kernels
-# (code objects), the chain kernel's own test, RCCL itself, wall-clock tests and the tests that interrupt a device-resident search from outside (the emulated device is
+# (code objects), RCCL itself, wall-clock tests and the tests that interrupt a device-resident search from outside (the emulated device is
 # synchronous: such a search would never end), the device's own libm check — and the full-size cases (hours on a CPU; ISRES above 2^20 individuals: > 10 min).
 #   bash tools/gpu_suite_on_emu.sh [extra pytest args]        (2-3 min with 6 workers; 400+ tests)
 cd "$(dirname "$0")/.." || exit 1
@@ -11,7 +11,6 @@ make -s -C oracle port emu emudev mockrccl || exit 1
 PYTHONPATH=tests NLA_TEST_EMU_DEVICE=1 python -m pytest -p _emu_plugin tests -m gpu -q -p no:cacheprovider -n "${JOBS:-6}" --timeout 600 --tb=line -rf \
     --deselect tests/test_gpu_fullsize.py --deselect tests/test_gpu_zz_clients.py --deselect tests/test_gpu_testopt_cli.py \
     --deselect tests/test_gpu_cpp_client.py --deselect tests/test_gpu_userobj.py --deselect tests/test_gpu_dropin.py \
-    --deselect tests/test_gpu_kernels.py::test_chain_kernel_resolves_the_window_like_the_sequential_statement \
     --deselect tests/test_gpu_chain_resolver.py::test_chain_kernel_with_the_dedicated_resolver \
     --deselect "tests/test_gpu_chain_resolver.py::test_the_resolver_changes_nothing_but_who_advances_the_chain[rastrigin-512-100000-2500]" \
     --deselect "tests/test_gpu_chain_resolver.py::test_the_resolver_changes_nothing_but_who_advances_the_chain[griewank-2048-100000-1500]" \
