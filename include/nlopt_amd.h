@@ -546,7 +546,7 @@ typedef struct { double minf_max, ftol_rel, ftol_abs, xtol_rel; int32_t maxeval,
 size_t nla_cobyla_work_doubles(int n, int ld, int count);      /* doubles of `work` (a search's state is in LDS: a token size) */
 size_t nla_cobyla_work_ints(int n, int count);                 /* ints of `iwork` (the same) */
 size_t nla_cobyla_lds_bytes(int n);                            /* LDS one search of n variables in a finite box takes (simplex, inverse, models, LP basis) */
-int nla_cobyla_fits(int n);                                    /* 1: that fits a compute unit's 160 KB (n <= 51) — beyond, the caller runs the host algorithm */
+int nla_cobyla_fits(int n);                                    /* 1: that fits a compute unit's 160 KB (n <= 51) — beyond, nla_k_cobyla_batch_global serves */
 /* replaces: cobyla_minimize (cobyla.c:181-271) as nlopt_optimize(LN_COBYLA) reaches it (optimize.c:836-851, with the memoized best
  * point of :450-508,1064-1071) for `count` independent starts at once, one WAVEFRONT per start, compiled-in device objectives only.
  * X: count x ld, starts in, results out; dx: the initial step (n, device) or NULL = nlopt_set_default_initial_step per start
@@ -556,6 +556,16 @@ int nla_cobyla_fits(int n);                                    /* 1: that fits a
  * call and X unchanged.  Callers run such boxes through nlopt_optimize(LN_COBYLA), which eliminates (mlsl_driver.c does). */
 int nla_k_cobyla_batch(int obj, int n, int ld, int count, const double *lb, const double *ub, const double *dx, double *X,
                        double *work, int *iwork, const nla_cobyla_params *params, nla_lbfgs_result *out, void *stream);
+/* The same search with its five matrices (simplex, inverse, vertex values, model gradients, LP basis) in a per-search slice of `work`
+ * in device memory and only the vectors in LDS: serves every 1 <= n <= NLA_COBYLA_GLOBAL_MAX_N (the slice is ~3.9 MB per search at
+ * n = 256, 1.2 GB for a batch of 320), small n included — there it is nla_k_cobyla_batch's search bit for bit, only slower.  Same
+ * arguments, results and fixed-coordinate refusal; `work` holds nla_cobyla_global_work_doubles(n, count) doubles (the kernel zeroes
+ * what it uses), `iwork` is not used.  Fails (hipErrorInvalidValue) when !nla_cobyla_global_fits(n). */
+#define NLA_COBYLA_GLOBAL_MAX_N 256
+int nla_cobyla_global_fits(int n);                             /* 1 for 1 <= n <= NLA_COBYLA_GLOBAL_MAX_N */
+size_t nla_cobyla_global_work_doubles(int n, int count);       /* doubles of `work` for `count` searches (0 when n does not fit) */
+int nla_k_cobyla_batch_global(int obj, int n, int ld, int count, const double *lb, const double *ub, const double *dx, double *X,
+                              double *work, int *iwork, const nla_cobyla_params *params, nla_lbfgs_result *out, void *stream);
 
 /* replaces: mma_minimize (mma.c:146-449) with m = 0 for `count` independent starts at once, one workgroup per start, outer
  * and inner iterations on the device (the 0-dimensional dual "solve" is dual_func's closed form, mma.c:58-137).  X: count x

@@ -130,7 +130,9 @@ nla_local_ctx *nla_local_ctx_create_cobyla(const nla_evaluator *ev, int n, int c
     c->alg = 2;
     c->d_sigma_init = d_dx;
     if (ctx_common(c, ev, n, cap, d_lb, d_ub, stream)) { nla_local_ctx_destroy(c); return NULL; }
-    c->d_work = (double *) nla_dev_malloc(sizeof(double) * nla_cobyla_work_doubles(n, c->ld, cap));
+    /* the workspace of whichever kernel serves n (launch()): a token for the LDS kernel, the searches' matrices for the global one */
+    c->d_work = (double *) nla_dev_malloc(sizeof(double) * (nla_cobyla_fits(n) || !nla_cobyla_global_serves(n) ? nla_cobyla_work_doubles(n, c->ld, cap)
+                                                                                                                 : nla_cobyla_global_work_doubles(n, cap)));
     c->d_iwork = (int *) nla_dev_malloc(sizeof(int) * nla_cobyla_work_ints(n, cap));
     c->h_lb = (double *) malloc(sizeof(double) * (size_t) n); c->h_ub = (double *) malloc(sizeof(double) * (size_t) n);
     c->h_rows = (double *) malloc(sizeof(double) * (size_t) c->ld * (size_t) cap);
@@ -141,8 +143,11 @@ nla_local_ctx *nla_local_ctx_create_cobyla(const nla_evaluator *ev, int n, int c
     /* One wavefront walks a search's serial chain 4 - 20 times slower than a host core (measured per evaluation of ONE search, device
      * against the reference on the same box, profiles/r06_cobyla_batched.txt: n = 8 21.7 us against 1.0, n = 16 40.6 against 4.2,
      * n = 32 133 against 26, n = 48 380 against 88) and hundreds of them run side by side (2048 searches: 56x / 104x one core at n = 8 / 16):
-     * the device is the faster place from about that many concurrent searches on, the host below */
-    c->cob_min_batch = n < 12 ? 24 : n < 24 ? 12 : 6;
+     * the device is the faster place from about that many concurrent searches on, the host below.  n > 51, the global-memory kernel
+     * (profiles/r07_cobyla_global.txt, per iteration behind the initial simplex): n = 52 1.14 ms against 0.14, n = 64 2.17 against
+     * 0.22, n = 128 16.1 against 2.5 — one search is 6 - 10 times a host core's time and up to 64 cost no more than one, so the
+     * device is ahead from 7 (n = 128) to 10 (n = 64) searches on */
+    c->cob_min_batch = n < 12 ? 24 : n < 24 ? 12 : nla_cobyla_fits(n) ? 6 : 10;
     return c;
 }
 /* ... the threshold can be set: 1 = every batch on the device, 0 / negative = the default above ("amd_cobyla_min_batch") */
@@ -238,7 +243,9 @@ static int launch(nla_local_ctx *c, int count, const nla_lbfgs_params *prm, cons
         P.minf_max = prm->minf_max; P.ftol_rel = prm->ftol_rel; P.ftol_abs = prm->ftol_abs; P.xtol_rel = prm->xtol_rel; P.maxeval = prm->maxeval;
         P.exact = (c->exact & 1); P.sign = c->ev.sign; P.xtol_abs = c->d_xtol_abs; P.abort = c->h_abort; P.done = c->d_done;
         if (ext) return -1;
-        return nla_k_cobyla_batch(obj, c->n, c->ld, count, c->d_lb, c->d_ub, c->d_sigma_init, c->d_X, c->d_work, c->d_iwork, &P, c->d_res, c->st);
+        /* the state in LDS while it fits there, its matrices in c->d_work beyond (nla_local_ctx_create_cobyla sized it so) */
+        return (nla_cobyla_fits(c->n) || !nla_cobyla_global_serves(c->n) ? nla_k_cobyla_batch : nla_k_cobyla_batch_global)
+                   (obj, c->n, c->ld, count, c->d_lb, c->d_ub, c->d_sigma_init, c->d_X, c->d_work, c->d_iwork, &P, c->d_res, c->st);
     } else if (c->alg == 1) {
         nla_mma_params P = c->mma;
         P.minf_max = prm->minf_max; P.ftol_rel = prm->ftol_rel; P.ftol_abs = prm->ftol_abs; P.xtol_rel = prm->xtol_rel; P.maxeval = prm->maxeval;

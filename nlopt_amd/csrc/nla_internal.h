@@ -254,6 +254,15 @@ nla_local_ctx *nla_local_ctx_create_mma(const nla_evaluator *ev, int n, int cap,
                                         const double *d_lb, const double *d_ub, void *stream);
 nla_local_ctx *nla_local_ctx_create_cobyla(const nla_evaluator *ev, int n, int cap, const double *d_dx, const double *d_lb, const double *d_ub, void *stream);
 void nla_local_ctx_set_cobyla_min_batch(nla_local_ctx *c, int min_batch);
+/* device COBYLA beyond the LDS kernel's dimensions (hip/cobyla_global.hip).  The drivers reach its two entry points through WEAK
+ * references: a device layer without them (the emulated one the CPU tests link) leaves them null, and such dimensions stay with the
+ * host algorithm.  1: the launcher is there and serves n. */
+extern __typeof(nla_k_cobyla_batch_global) nla_k_cobyla_batch_global __attribute__((weak));
+extern __typeof(nla_cobyla_global_work_doubles) nla_cobyla_global_work_doubles __attribute__((weak));
+static inline int nla_cobyla_global_serves(int n)
+{
+    return nla_k_cobyla_batch_global && nla_cobyla_global_work_doubles && n >= 1 && n <= NLA_COBYLA_GLOBAL_MAX_N;
+}
 int nla_local_ctx_alg(const nla_local_ctx *c);
 void nla_local_ctx_destroy(nla_local_ctx *c);
 double *nla_local_ctx_X(nla_local_ctx *c);

@@ -29,28 +29,42 @@ class Result(C.Structure):
     _fields_ = [("f", C.c_double), ("ret", C.c_int32), ("nevals", C.c_int32), ("iterm", C.c_int32), ("cols", C.c_int32)]
 
 
-def build():
-    os.makedirs(os.path.dirname(OUT), exist_ok=True)
-    srcs = [os.path.join(HIP, "cobyla_kernels.hip")]
-    deps = srcs + [os.path.join(HIP, "local_common.h"), os.path.join(HIP, "dev_common.h")]
-    if os.path.exists(OUT) and all(os.path.getmtime(OUT) > os.path.getmtime(s) for s in deps):
-        return
+OUT_GLOBAL = os.path.join(ROOT, "tools", "_build", "libcobyla_global_emu.so")
+
+
+def build(src="cobyla_kernels.hip", out=OUT):
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    srcs = [os.path.join(HIP, src)]
+    deps = srcs + [os.path.join(HIP, "cobyla_search.h"), os.path.join(HIP, "local_common.h"), os.path.join(HIP, "dev_common.h")]
+    if os.path.exists(out) and all(os.path.getmtime(out) > os.path.getmtime(s) for s in deps):
+        return out
     subprocess.run(["g++", "-O1", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-x", "c++", "-w", "-I", os.path.join(ROOT, "tools", "simt_emu"),
-                    "-o", OUT] + srcs + ["-lpthread"], check=True)
+                    "-o", out] + srcs + ["-lpthread"], check=True)
+    return out
 
 
-def run(L, obj, n, starts, lo, hi, xtol_rel=1e-6, maxeval=0, ftol_rel=0.0, dx=None, exact=1, sign=1.0, minf_max=-np.inf):
+def build_global():
+    """hip/cobyla_global.hip (the same search, its matrices in a global-memory workspace) the same way: tests/test_cobyla_global_emu.py"""
+    return build("cobyla_global.hip", OUT_GLOBAL)
+
+
+def run(L, obj, n, starts, lo, hi, xtol_rel=1e-6, maxeval=0, ftol_rel=0.0, dx=None, exact=1, sign=1.0, minf_max=-np.inf, entry="nla_k_cobyla_batch"):
     count, ld = starts.shape[0], (n + 1) & ~1
     X = np.zeros((count, ld)); X[:, :n] = starts
     lb = np.ascontiguousarray(lo, dtype=np.float64); ub = np.ascontiguousarray(hi, dtype=np.float64)
-    work = np.zeros(max(8, count * 8)); iwork = np.zeros(max(8, count * 8), dtype=np.int32)
+    nwork = max(8, count * 8)
+    if entry == "nla_k_cobyla_batch_global":
+        L.nla_cobyla_global_work_doubles.restype = C.c_size_t
+        nwork = L.nla_cobyla_global_work_doubles(n, count)
+    work = np.full(nwork, np.nan if entry == "nla_k_cobyla_batch_global" else 0.0); iwork = np.zeros(max(8, count * 8), dtype=np.int32)        # (the global kernel zeroes what it uses itself)
     res = (Result * count)()
     P = Params(minf_max, ftol_rel, 0.0, xtol_rel, maxeval, exact, sign, None, None, None)
     vp = C.c_void_p
-    L.nla_k_cobyla_batch.argtypes = [C.c_int] * 4 + [vp] * 6 + [C.POINTER(Params), vp, vp]
-    L.nla_k_cobyla_batch.restype = C.c_int
-    rc = L.nla_k_cobyla_batch(O.OBJ[obj], n, ld, count, lb.ctypes.data, ub.ctypes.data, dx.ctypes.data if dx is not None else None, X.ctypes.data,
-                              work.ctypes.data, iwork.ctypes.data, C.byref(P), C.cast(res, vp), None)
+    fn = getattr(L, entry)
+    fn.argtypes = [C.c_int] * 4 + [vp] * 6 + [C.POINTER(Params), vp, vp]
+    fn.restype = C.c_int
+    rc = fn(O.OBJ[obj], n, ld, count, lb.ctypes.data, ub.ctypes.data, dx.ctypes.data if dx is not None else None, X.ctypes.data,
+            work.ctypes.data, iwork.ctypes.data, C.byref(P), C.cast(res, vp), None)
     assert rc == 0, rc
     return dict(x=X[:, :n].copy(), f=np.array([r.f for r in res]), ret=[r.ret for r in res], nevals=[r.nevals for r in res])
 
