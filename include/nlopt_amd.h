@@ -481,7 +481,13 @@ int nla_k_isres_evolve_parent_mu(int n, int ld, int64_t survivors, const double 
  * evaluation of a search (plis.c:260,390; mma.c:219,297,337) the kernel writes the point into row `inst` of EX, sets
  * req[inst] = {1, gradient wanted?} and returns; the caller evaluates, stores f in EF[inst] and the gradient in row inst of
  * EG, and launches the same kernel again with resume = 1; req[inst].state == 2: the search has finished (out[inst] valid).
- * All pointers are device pointers. */
+ * All pointers are device pointers.
+ * LN_COBYLA (nla_k_cobyla_batch_ext) follows the same contract at its one evaluation point (cobyla.c:582): want_grad is always 0
+ * and EG is never touched; EF[inst] is taken AS DELIVERED (the caller applies the sign of a maximisation, params->sign is not
+ * applied again); `forced` / `timeout` are looked at in front of every evaluation (cobyla.c:574-578); save holds
+ * nla_cobyla_save_bytes(n) bytes per search.  With resume = 0 every search starts, whatever req holds; with resume = 1 a search
+ * whose state is not 1 is left alone, so a finished search stays finished through every later launch.  No launch waits for
+ * anything: it runs each search to its next evaluation or its end and returns. */
 #define NLA_OBJ_EXTERNAL (-1)
 /* OR-ed into a compiled-in objective id given to a kernel launcher (nla_k_eval, nla_k_crs_init_rows, nla_k_crs_finish*,
  * nla_k_crs_chain, nla_k_isres_eval): the kernel delivers -f — how nlopt_set_max_objective keeps a device objective on the
@@ -491,7 +497,7 @@ typedef struct { int32_t state, want_grad; } nla_local_req;
 typedef struct {
     nla_local_req *req;            /* count entries */
     double *EX, *EG, *EF;          /* count x ld points; count x ld gradients; count values */
-    void *save;                    /* count x nla_lbfgs_save_bytes() / nla_mma_save_bytes() */
+    void *save;                    /* count x nla_lbfgs_save_bytes() / nla_mma_save_bytes() / nla_cobyla_save_bytes(n) */
     int32_t resume;                /* 0: start the searches; 1: continue those whose evaluation was delivered */
     int32_t forced, timeout;       /* the caller's nlopt_force_stop flag / maxtime verdict at this launch (stop.c:141-159) */
     int32_t pad;
@@ -548,7 +554,8 @@ size_t nla_cobyla_work_ints(int n, int count);                 /* ints of `iwork
 size_t nla_cobyla_lds_bytes(int n);                            /* LDS one search of n variables in a finite box takes (simplex, inverse, models, LP basis) */
 int nla_cobyla_fits(int n);                                    /* 1: that fits a compute unit's 160 KB (n <= 51) — beyond, nla_k_cobyla_batch_global serves */
 /* replaces: cobyla_minimize (cobyla.c:181-271) as nlopt_optimize(LN_COBYLA) reaches it (optimize.c:836-851, with the memoized best
- * point of :450-508,1064-1071) for `count` independent starts at once, one WAVEFRONT per start, compiled-in device objectives only.
+ * point of :450-508,1064-1071) for `count` independent starts at once, one WAVEFRONT per start, compiled-in device objectives (any
+ * other objective: nla_k_cobyla_batch_ext below).
  * X: count x ld, starts in, results out; dx: the initial step (n, device) or NULL = nlopt_set_default_initial_step per start
  * (options.c:921-946); out[i] = (f, nlopt_result, objective calls, the same, 0).  Fails (hipErrorInvalidValue) when !nla_cobyla_fits(n).
  * Precondition: lb[j] < ub[j] for every j — a fixed coordinate (lb[j] == ub[j]) is not eliminated here as the reference eliminates it
@@ -566,6 +573,18 @@ int nla_cobyla_global_fits(int n);                             /* 1 for 1 <= n <
 size_t nla_cobyla_global_work_doubles(int n, int count);       /* doubles of `work` for `count` searches (0 when n does not fit) */
 int nla_k_cobyla_batch_global(int obj, int n, int ld, int count, const double *lb, const double *ub, const double *dx, double *X,
                               double *work, int *iwork, const nla_cobyla_params *params, nla_lbfgs_result *out, void *stream);
+/* The same search again, storage as nla_k_cobyla_batch_global, for an objective OUTSIDE this library (a user-supplied device objective):
+ * a coroutine by the contract of "External evaluation" above (hip/cobyla_ext.hip).  Serves 1 <= n <= NLA_COBYLA_GLOBAL_MAX_N; `work`
+ * holds nla_cobyla_ext_work_doubles(n, count) doubles (a starting search zeroes what it uses), ext->save nla_cobyla_save_bytes(n)
+ * bytes per search; params->abort and params->done are not used (ext->forced / ext->timeout, req[].state == 2), nor is params->exact
+ * (the sums of the objective are the caller's).  Results and the fixed-coordinate refusal (then req[i].state = 2 at once, no
+ * evaluation requested) as nla_k_cobyla_batch.  Refuses with hipErrorInvalidValue, launching nothing, when n is outside that range,
+ * ld < n, or work, ext or one of ext->req / EX / EF / save is NULL; count <= 0 returns 0. */
+size_t nla_cobyla_ext_work_doubles(int n, int count);          /* doubles of `work` for `count` searches (0 when n is not served) */
+size_t nla_cobyla_save_bytes(int n);                           /* per search, of nla_local_ext.save (0 when n is not served) */
+int nla_k_cobyla_batch_ext(int n, int ld, int count, const double *lb, const double *ub, const double *dx, double *X,
+                           double *work, const nla_cobyla_params *params, nla_lbfgs_result *out,
+                           const nla_local_ext *ext, void *stream);
 
 /* replaces: mma_minimize (mma.c:146-449) with m = 0 for `count` independent starts at once, one workgroup per start, outer
  * and inner iterations on the device (the 0-dimensional dual "solve" is dual_func's closed form, mma.c:58-137).  X: count x

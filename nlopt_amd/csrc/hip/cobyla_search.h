@@ -4,6 +4,9 @@
  *   cobyla_kernels.hip   cw_search<OBJ, 0>: the whole state in LDS (n <= 51)
  *   cobyla_global.hip    cw_search<OBJ, 1>: SIM, SIMI, DAT, A and Z in a per-search slice of a global-memory workspace, the vectors,
  *                        iact and rot in LDS (n <= NLA_COBYLA_GLOBAL_MAX_N)
+ *   cobyla_ext.hip       cw_search<0, 2>: the storage of the global instance, the objective OUTSIDE the kernel — the search is a coroutine
+ *                        (include/nlopt_amd.h "External evaluation") that leaves at its one evaluation point and is entered again
+ *                        behind it, its scalars and its LDS block kept in a save record between the two launches (cw_saved)
  * The search touches its arrays only through the pointers of cw_ws. */
 #ifndef NLA_COBYLA_SEARCH_H
 #define NLA_COBYLA_SEARCH_H
@@ -90,6 +93,18 @@ __host__ __device__ static inline size_t cw_vec_doubles(int n, int m)
 {
     return 14 * (size_t) n + 6 * (size_t) cw_vlen(n, m) + ((size_t) (m + 2) + (size_t) n + 1) / 2 + 1;
 }
+
+/* The coroutine instance (hip/cobyla_ext.hip) between two launches: what of a search is neither in its slice of the workspace nor
+ * recomputed from the arguments — the scalars that are live across the evaluation point, and behind them the LDS block of the global
+ * instance as it stands (cw_vec_doubles(n, m) doubles: the vectors, iact and rot) */
+struct cw_saved {
+    double rho, parmu, parsig, prerec, prerem, resmax, minf, bestf, rhobeg, rhoend;
+    int32_t jdrop, ibrnch, iflag, ifull, nevals, rc, m;
+    uint32_t seed;
+};
+#define CW_SAVED_DOUBLES ((sizeof(cw_saved) + 7) / 8)
+/* doubles of one search's save record: sized for a fully finite box, a whole number of 128-byte lines */
+__host__ __device__ static inline size_t cw_save_doubles(int n) { return (CW_SAVED_DOUBLES + cw_vec_doubles(n, 2 * n) + 15) & ~(size_t) 15; }
 
 #define SIM(i, j)  W.sim[(j) * W.ldn + (i)]            /* j < n: displacement of vertex j from the pole; j == n: the pole                cobyla.c:493-497 */
 #define SIMI(j, i) W.simi[(i) * W.ldn + (j)]           /* inverse of the displacement matrix */
@@ -422,20 +437,33 @@ __device__ static void cw_replace_vertex(const cw_ws &W, int jdrop, int after_re
 static double cw_lds[24576];                                                                  /* (the CPU emulation runs one workgroup at a time) */
 #endif
 
-/* ONE search by one wavefront: the body of both kernels.  GLOBAL = 0 (cobyla_kernels.hip): the whole state in the LDS block `cw_lds`,
+/* ONE search by one wavefront: the body of all kernels.  GLOBAL = 0 (cobyla_kernels.hip): the whole state in the LDS block `cw_lds`,
  * `gw` unused.  GLOBAL = 1 (cobyla_global.hip): the matrices in this search's slice `gw` of the workspace, the rest in `cw_lds`.  Only
  * the addresses differ: every sum, every decision and the result record are the same statements.  S, oscratch, XB: the kernel's LDS
- * buffers for the reductions and the exact-order objective. */
+ * buffers for the reductions and the exact-order objective.
+ * GLOBAL = 2 (cobyla_ext.hip, EXT below): the storage of GLOBAL = 1, and the objective is the caller's — at EVAL_PRE, behind the stop
+ * tests, the search writes its point to row `inst` of E.EX, its state to its record of E.save, sets E.req[inst] = {1, 0} and RETURNS;
+ * launched again with E.resume = 1 it restores that state, takes f = E.EF[inst] as delivered (the caller has applied the sign) and goes
+ * on at EVAL_MEMO.  E.forced / E.timeout stand in for the abort flag, E.req[inst].state = 2 for the finished counter; OBJ, oscratch and
+ * XB are not used.  Nothing in it waits: a launch runs every search to its next evaluation point or its end. */
 template <int OBJ, int GLOBAL>
 __device__ __forceinline__ void cw_search(int n, int ld, int count, const double *__restrict__ lb, const double *__restrict__ ub,
                                           const double *__restrict__ dx_given, double *__restrict__ X, nla_cobyla_params P,
-                                          nla_lbfgs_result *__restrict__ out, double *cw_lds, double *gw, lb_shared &S, double *oscratch, lb_exact_buf &XB)
+                                          nla_lbfgs_result *__restrict__ out, double *cw_lds, double *gw, lb_shared &S, double *oscratch, lb_exact_buf &XB,
+                                          const nla_local_ext &E = nla_local_ext())
 {
+    constexpr bool EXT = GLOBAL == 2;
     const int inst = blockIdx.x, lane = threadIdx.x;
     if (inst >= count) return;
+    /* the coroutine: a launch that resumes concerns the searches that wait for their value (state 1) — a finished one (2) stays as it
+     * is.  (Every lane reads the same word, and a barrier stands between this read and the store that ends the launch.) */
+    if (EXT && E.resume && E.req[inst].state != 1) return;
+    const bool resumed = EXT && E.resume;
+    cw_saved *sv = EXT ? (cw_saved *) ((double *) E.save + (size_t) inst * cw_save_doubles(n)) : nullptr;
+    double *svec = EXT ? (double *) sv + CW_SAVED_DOUBLES : nullptr;
     double *x0 = X + (size_t) inst * ld;
     const double alpha = .25, beta = 2.1, gamma_ = .5, delta = 1.1;
-    enum { EVAL_PRE, EVAL_POST, POLE, TRUST_STEP, JUDGE, SHRINK, FINISH_POLE, FINISH_HERE, FINISHED };
+    enum { EVAL_PRE, EVAL_MEMO, EVAL_POST, POLE, TRUST_STEP, JUDGE, SHRINK, FINISH_POLE, FINISH_HERE, FINISHED };
     int i, j, k, m = 0;
 
     /* the number of rows first: the finite bounds (cobyla.c:233-241) */
@@ -447,7 +475,8 @@ __device__ __forceinline__ void cw_search(int n, int ld, int count, const double
     if (fixed) {
         if (lane == 0) {
             out[inst].f = __builtin_huge_val(); out[inst].ret = CW_INVALID_ARGS; out[inst].nevals = 0; out[inst].iterm = 0; out[inst].cols = 0;
-            if (P.done) __hip_atomic_fetch_add(P.done, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (EXT) { E.req[inst].state = 2; E.req[inst].want_grad = 0; }
+            else if (P.done) __hip_atomic_fetch_add(P.done, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
         return;
     }
@@ -469,78 +498,90 @@ __device__ __forceinline__ void cw_search(int n, int ld, int count, const double
     }
     const int np = n, mp = m, mpp = m + 1;        /* the pole's column, the objective's row, the violation's row */
     const size_t total = GLOBAL ? cw_vec_doubles(n, m) : cw_lds_doubles(n, m);
-    for (size_t e = lane; e < total; e += CW_LANES) cw_lds[e] = 0.;
-    if (GLOBAL) { const size_t gtotal = cw_global_doubles(n, m); for (size_t e = lane; e < gtotal; e += CW_LANES) gw[e] = 0.; }
-    CW_SYNC();
-
-    /* ---- set-up ---- */
+    /* ---- set-up (a resumed search: its LDS block back from the save record instead; the slice is as the last launch left it) ---- */
     int bad = 0;
-    double rhobeg, rhoend;
-    /* the initial step: the caller's, or nlopt_set_default_initial_step(opt, x) (options.c:921-946) — a quarter of the box, or 3/4 of the
-     * gap to a bound that is nearer than that */
-    for (j = lane; j < n; j += CW_LANES) {
-        double step;
-        if (dx_given) step = dx_given[j];
-        else {
-            const double lo = lb[j], hi = ub[j], xj = x0[j];
-            step = __builtin_huge_val();
-            if (!cw_isinf(hi) && !cw_isinf(lo) && (hi - lo) * 0.25 < step && hi > lo) step = (hi - lo) * 0.25;
-            if (!cw_isinf(hi) && hi - xj < step && hi > xj) step = (hi - xj) * 0.75;
-            if (!cw_isinf(lo) && xj - lo < step && xj > lo) step = (xj - lo) * 0.75;
-            if (cw_isinf(step)) {
-                if (!cw_isinf(hi) && fabs(hi - xj) < fabs(step)) step = (hi - xj) * 1.1;
-                if (!cw_isinf(lo) && fabs(xj - lo) < fabs(step)) step = (xj - lo) * 1.1;
-            }
-            if (cw_isinf(step) || cw_istiny(step)) step = xj;
-            if (cw_isinf(step) || step == 0.0) step = 1;
-        }
-        W.step0[j] = step;
+    double rhobeg = 0., rhoend = 0.;
+    if (resumed) for (size_t e = lane; e < total; e += CW_LANES) cw_lds[e] = svec[e];
+    else {
+        for (size_t e = lane; e < total; e += CW_LANES) cw_lds[e] = 0.;
+        if (GLOBAL) { const size_t gtotal = cw_global_doubles(n, m); for (size_t e = lane; e < gtotal; e += CW_LANES) gw[e] = 0.; }
     }
     CW_SYNC();
-    /* nlopt_compute_rescaling (rescale.c:30-48), the scaled box and point (cobyla.c:200-232) */
-    {
-        int uniform = 1;
-        for (j = 1; j < n; ++j) if (W.step0[j] != W.step0[j - 1]) { uniform = 0; break; }
-        const double d0 = W.step0[0];
-        rhobeg = fabs(d0 / 1.0);
-        rhoend = P.xtol_rel * rhobeg;
-        for (j = 0; j < n; ++j) {
-            const double sc = (uniform || j == 0) ? 1.0 : W.step0[j] / d0;
-            if (sc == 0 || !isfinite(sc)) bad = 1;
-            if (P.xtol_abs && rhoend < P.xtol_abs[j] / fabs(sc)) rhoend = P.xtol_abs[j] / fabs(sc);
-            if (lane == (j & (CW_LANES - 1))) {
-                double l = lb[j] / sc, u = ub[j] / sc;
-                if (l > u) { const double t = l; l = u; u = t; }
-                W.scale[j] = sc; W.slb[j] = l; W.sub[j] = u; W.x[j] = x0[j] / sc;
+    if (!resumed) {
+        /* the initial step: the caller's, or nlopt_set_default_initial_step(opt, x) (options.c:921-946) — a quarter of the box, or 3/4 of the
+         * gap to a bound that is nearer than that */
+        for (j = lane; j < n; j += CW_LANES) {
+            double step;
+            if (dx_given) step = dx_given[j];
+            else {
+                const double lo = lb[j], hi = ub[j], xj = x0[j];
+                step = __builtin_huge_val();
+                if (!cw_isinf(hi) && !cw_isinf(lo) && (hi - lo) * 0.25 < step && hi > lo) step = (hi - lo) * 0.25;
+                if (!cw_isinf(hi) && hi - xj < step && hi > xj) step = (hi - xj) * 0.75;
+                if (!cw_isinf(lo) && xj - lo < step && xj > lo) step = (xj - lo) * 0.75;
+                if (cw_isinf(step)) {
+                    if (!cw_isinf(hi) && fabs(hi - xj) < fabs(step)) step = (hi - xj) * 1.1;
+                    if (!cw_isinf(lo) && fabs(xj - lo) < fabs(step)) step = (xj - lo) * 1.1;
+                }
+                if (cw_isinf(step) || cw_istiny(step)) step = xj;
+                if (cw_isinf(step) || step == 0.0) step = 1;
+            }
+            W.step0[j] = step;
+        }
+        CW_SYNC();
+        /* nlopt_compute_rescaling (rescale.c:30-48), the scaled box and point (cobyla.c:200-232) */
+        {
+            int uniform = 1;
+            for (j = 1; j < n; ++j) if (W.step0[j] != W.step0[j - 1]) { uniform = 0; break; }
+            const double d0 = W.step0[0];
+            rhobeg = fabs(d0 / 1.0);
+            rhoend = P.xtol_rel * rhobeg;
+            for (j = 0; j < n; ++j) {
+                const double sc = (uniform || j == 0) ? 1.0 : W.step0[j] / d0;
+                if (sc == 0 || !isfinite(sc)) bad = 1;
+                if (P.xtol_abs && rhoend < P.xtol_abs[j] / fabs(sc)) rhoend = P.xtol_abs[j] / fabs(sc);
+                if (lane == (j & (CW_LANES - 1))) {
+                    double l = lb[j] / sc, u = ub[j] / sc;
+                    if (l > u) { const double t = l; l = u; u = t; }
+                    W.scale[j] = sc; W.slb[j] = l; W.sub[j] = u; W.x[j] = x0[j] / sc;
+                }
             }
         }
-    }
-    CW_SYNC();
+        CW_SYNC();
 
-    /* the initial simplex: the pole at x, vertex i one step along coordinate i, the step kept inside the box (cobyla.c:538-562) */
-    for (i = lane; i < n; i += CW_LANES) {
-        double rhocur = rhobeg;
-        const double xi = W.x[i];
-        SIM(i, np) = xi;
-        if (xi + rhocur > W.sub[i]) {
-            if (xi - rhocur >= W.slb[i]) rhocur = -rhocur;
-            else if (W.sub[i] - xi > xi - W.slb[i]) rhocur = 0.5 * (W.sub[i] - xi);
-            else rhocur = 0.5 * (xi - W.slb[i]);
+        /* the initial simplex: the pole at x, vertex i one step along coordinate i, the step kept inside the box (cobyla.c:538-562) */
+        for (i = lane; i < n; i += CW_LANES) {
+            double rhocur = rhobeg;
+            const double xi = W.x[i];
+            SIM(i, np) = xi;
+            if (xi + rhocur > W.sub[i]) {
+                if (xi - rhocur >= W.slb[i]) rhocur = -rhocur;
+                else if (W.sub[i] - xi > xi - W.slb[i]) rhocur = 0.5 * (W.sub[i] - xi);
+                else rhocur = 0.5 * (xi - W.slb[i]);
+            }
+            SIM(i, i) = rhocur;
+            SIMI(i, i) = 1.0 / rhocur;
         }
-        SIM(i, i) = rhocur;
-        SIMI(i, i) = 1.0 / rhocur;
+        CW_SYNC();
     }
-    CW_SYNC();
 
     double rho = rhobeg, parmu = 0., parsig = 0., pareta, prerec = 0., prerem = 0., f = 0., resmax = 0., temp, tempa, sum = 0., minf = __builtin_huge_val();
     double bestf = DBL_MAX;
     int jdrop = np, ibrnch = 0, iflag = 0, ifull = 0, nbest, go = EVAL_PRE, rc = CW_SUCCESS, nevals = 0, forced = 0, timed = 0;
     uint32_t seed = (uint32_t) (n + m);
     if (bad) { rc = CW_INVALID_ARGS /* invalid scaling (cobyla.c:207-212) */; go = FINISHED; }
+    if (EXT) { forced = E.forced; timed = E.timeout; }            /* the caller's verdicts at this launch */
+    if (resumed) {                                                /* behind the evaluation this search left at: the value is the caller's */
+        rho = sv->rho; parmu = sv->parmu; parsig = sv->parsig; prerec = sv->prerec; prerem = sv->prerem; resmax = sv->resmax; minf = sv->minf;
+        bestf = sv->bestf; rhobeg = sv->rhobeg; rhoend = sv->rhoend; jdrop = sv->jdrop; ibrnch = sv->ibrnch; iflag = sv->iflag; ifull = sv->ifull;
+        nevals = sv->nevals; rc = sv->rc; seed = sv->seed;
+        f = E.EF[inst];
+        go = EVAL_MEMO;
+    }
 
     while (go != FINISHED) switch (go) {
     case EVAL_PRE: {                                              /* L40 (cobyla.c:573-631): the stop tests in front of an evaluation */
-        if (P.abort) { const int ab = lb_poll_abort(P.abort); forced = ab == -999; timed = ab == 100; }
+        if (!EXT && P.abort) { const int ab = lb_poll_abort(P.abort); forced = ab == -999; timed = ab == 100; }
         if (forced) rc = CW_FORCED_STOP;
         else if (nevals > 0) {
             if (P.maxeval > 0 && nevals >= P.maxeval) rc = CW_MAXEVAL_REACHED;
@@ -555,9 +596,23 @@ __device__ __forceinline__ void cw_search(int n, int ld, int count, const double
             W.xev[j] = v * W.scale[j];
         }
         CW_SYNC();
+        if (EXT) {                                                /* the coroutine leaves: the point, the LDS block, the scalars, the request */
+            for (j = lane; j < n; j += CW_LANES) E.EX[(size_t) inst * ld + j] = W.xev[j];
+            for (size_t e = lane; e < total; e += CW_LANES) svec[e] = cw_lds[e];
+            if (lane == 0) {
+                sv->rho = rho; sv->parmu = parmu; sv->parsig = parsig; sv->prerec = prerec; sv->prerem = prerem; sv->resmax = resmax; sv->minf = minf;
+                sv->bestf = bestf; sv->rhobeg = rhobeg; sv->rhoend = rhoend; sv->jdrop = jdrop; sv->ibrnch = ibrnch; sv->iflag = iflag; sv->ifull = ifull;
+                sv->nevals = nevals; sv->rc = rc; sv->m = m; sv->seed = seed;
+                E.req[inst].state = 1; E.req[inst].want_grad = 0;
+            }
+            return;
+        }
         if (P.exact) { nla_obj_part t; f = lb_obj_exact<OBJ>(n, W.xev, &t, XB); }
         else f = nla_block_objective_as<OBJ, 1, 4>(n, [&](int q) { return W.xev[q]; }, oscratch);      /* the bits of the other local optimisers' 256-thread reduction */
         f *= P.sign;
+    }
+    /* fall through */
+    case EVAL_MEMO: {                                             /* (where a resumed search comes in) */
         {   /* memoize_func (optimize.c:450-483): the best value seen at a point inside the caller's box */
             int outside = 0;
             for (j = lane; j < n; j += CW_LANES) if (W.xev[j] < lb[j] || W.xev[j] > ub[j]) outside = 1;
@@ -902,7 +957,8 @@ __device__ __forceinline__ void cw_search(int n, int ld, int count, const double
     if (lane == 0) {
         out[inst].f = bestf < DBL_MAX ? bestf : minf;
         out[inst].ret = rc; out[inst].nevals = nevals; out[inst].iterm = nevals; out[inst].cols = 0;
-        if (P.done) __hip_atomic_fetch_add(P.done, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (EXT) { E.req[inst].state = 2; E.req[inst].want_grad = 0; }
+        else if (P.done) __hip_atomic_fetch_add(P.done, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     (void) tempa; (void) pareta;
 }

@@ -81,7 +81,8 @@ void nla_local_ctx_destroy(nla_local_ctx *c)
 
 static int ctx_common(nla_local_ctx *c, const nla_evaluator *ev, int n, int cap, const double *d_lb, const double *d_ub, void *stream)
 {
-    const size_t save = c->alg == 1 ? nla_mma_save_bytes() : nla_lbfgs_save_bytes();
+    /* (alg 2 comes here with an external objective only where nla_cobyla_ext_serves(n): nla_local_ctx_create_cobyla) */
+    const size_t save = c->alg == 2 ? (ev->kind != NLA_EVAL_DEVICE ? nla_cobyla_save_bytes(n) : 0) : c->alg == 1 ? nla_mma_save_bytes() : nla_lbfgs_save_bytes();
     c->ev = *ev; c->n = n; c->ld = (n + 1) & ~1; c->cap = cap; c->st = stream; c->d_lb = d_lb; c->d_ub = d_ub;
     c->d_X = (double *) nla_dev_malloc(sizeof(double) * (size_t) c->ld * (size_t) cap);
     c->d_res = (nla_lbfgs_result *) nla_dev_malloc(sizeof(nla_lbfgs_result) * (size_t) cap);
@@ -92,7 +93,7 @@ static int ctx_common(nla_local_ctx *c, const nla_evaluator *ev, int n, int cap,
     if (ev->kind != NLA_EVAL_DEVICE) {
         c->ext.req = (nla_local_req *) nla_dev_malloc(sizeof(nla_local_req) * (size_t) cap);
         c->ext.EX = (double *) nla_dev_malloc(sizeof(double) * (size_t) c->ld * (size_t) cap);
-        c->ext.EG = (double *) nla_dev_malloc(sizeof(double) * (size_t) c->ld * (size_t) cap);
+        c->ext.EG = (double *) nla_dev_malloc(sizeof(double) * (c->alg == 2 ? 8 : (size_t) c->ld * (size_t) cap));      /* (LN_COBYLA never wants a gradient: a token) */
         c->ext.EF = (double *) nla_dev_malloc(sizeof(double) * (size_t) cap);
         c->ext.save = nla_dev_malloc(save * (size_t) cap);
         c->h_req = (nla_local_req *) nla_host_malloc(sizeof(nla_local_req) * (size_t) cap);
@@ -119,19 +120,21 @@ nla_local_ctx *nla_local_ctx_create(const nla_evaluator *ev, int n, int cap, int
     if (!c->d_work || !c->d_iwork || !c->d_hist) { nla_local_ctx_destroy(c); return NULL; }
     return c;
 }
-/* the same for LN_COBYLA with bound constraints only (alg 2; hip/cobyla_kernels.hip: GN_MLSL's default local optimiser, compiled-in device
- * objectives only): d_dx = the initial step on the device, or NULL = the default step of every start (options.c:921-946) */
+/* the same for LN_COBYLA with bound constraints only (alg 2: GN_MLSL's default local optimiser; hip/cobyla_kernels.hip / cobyla_global.hip
+ * for a compiled-in device objective, hip/cobyla_ext.hip — the search as a coroutine, its evaluations by nla_local_ctx_run's loop — for a
+ * user-supplied one; NULL for a host callback or a dimension the coroutine does not serve): d_dx = the initial step on the device, or NULL = the default step of every start (options.c:921-946) */
 nla_local_ctx *nla_local_ctx_create_cobyla(const nla_evaluator *ev, int n, int cap, const double *d_dx, const double *d_lb, const double *d_ub, void *stream)
 {
     nla_local_ctx *c;
-    if (ev->kind != NLA_EVAL_DEVICE) return NULL;
+    if (ev->kind != NLA_EVAL_DEVICE && !(ev->kind == NLA_EVAL_USER && nla_cobyla_ext_serves(n))) return NULL;
     c = (nla_local_ctx *) calloc(1, sizeof *c);
     if (!c) return NULL;
     c->alg = 2;
     c->d_sigma_init = d_dx;
     if (ctx_common(c, ev, n, cap, d_lb, d_ub, stream)) { nla_local_ctx_destroy(c); return NULL; }
     /* the workspace of whichever kernel serves n (launch()): a token for the LDS kernel, the searches' matrices for the global one */
-    c->d_work = (double *) nla_dev_malloc(sizeof(double) * (nla_cobyla_fits(n) || !nla_cobyla_global_serves(n) ? nla_cobyla_work_doubles(n, c->ld, cap)
+    c->d_work = (double *) nla_dev_malloc(sizeof(double) * (ev->kind == NLA_EVAL_USER ? nla_cobyla_ext_work_doubles(n, cap)
+                                                            : nla_cobyla_fits(n) || !nla_cobyla_global_serves(n) ? nla_cobyla_work_doubles(n, c->ld, cap)
                                                                                                                  : nla_cobyla_global_work_doubles(n, cap)));
     c->d_iwork = (int *) nla_dev_malloc(sizeof(int) * nla_cobyla_work_ints(n, cap));
     c->h_lb = (double *) malloc(sizeof(double) * (size_t) n); c->h_ub = (double *) malloc(sizeof(double) * (size_t) n);
@@ -148,10 +151,17 @@ nla_local_ctx *nla_local_ctx_create_cobyla(const nla_evaluator *ev, int n, int c
      * 0.22, n = 128 16.1 against 2.5 — one search is 6 - 10 times a host core's time and up to 64 cost no more than one, so the
      * device is ahead from 7 (n = 128) to 10 (n = 64) searches on */
     c->cob_min_batch = n < 12 ? 24 : n < 24 ? 12 : nla_cobyla_fits(n) ? 6 : 10;
+    /* A user's kernel has no host twin that is guaranteed to give its bits, and a run's result must not depend on how its searches happen
+     * to be batched: every batch of such an objective, a lone search included, runs on the device */
+    if (ev->kind == NLA_EVAL_USER) c->cob_min_batch = 1;
     return c;
 }
-/* ... the threshold can be set: 1 = every batch on the device, 0 / negative = the default above ("amd_cobyla_min_batch") */
-void nla_local_ctx_set_cobyla_min_batch(nla_local_ctx *c, int min_batch) { if (c && c->alg == 2 && min_batch > 0) c->cob_min_batch = min_batch; }
+/* ... the threshold can be set: 1 = every batch on the device, 0 / negative = the default above ("amd_cobyla_min_batch"); not for a user's
+ * kernel, whose threshold stays 1 */
+void nla_local_ctx_set_cobyla_min_batch(nla_local_ctx *c, int min_batch)
+{
+    if (c && c->alg == 2 && c->ev.kind == NLA_EVAL_DEVICE && min_batch > 0) c->cob_min_batch = min_batch;
+}
 /* the same for LD_MMA (mma_driver.c reads the parameters; sigma_init: device copy of the initial step or NULL) */
 nla_local_ctx *nla_local_ctx_create_mma(const nla_evaluator *ev, int n, int cap, const nla_mma_params *alg_params, const double *d_sigma_init,
                                         const double *d_lb, const double *d_ub, void *stream)
@@ -242,7 +252,7 @@ static int launch(nla_local_ctx *c, int count, const nla_lbfgs_params *prm, cons
         memset(&P, 0, sizeof P);
         P.minf_max = prm->minf_max; P.ftol_rel = prm->ftol_rel; P.ftol_abs = prm->ftol_abs; P.xtol_rel = prm->xtol_rel; P.maxeval = prm->maxeval;
         P.exact = (c->exact & 1); P.sign = c->ev.sign; P.xtol_abs = c->d_xtol_abs; P.abort = c->h_abort; P.done = c->d_done;
-        if (ext) return -1;
+        if (ext) return nla_k_cobyla_batch_ext(c->n, c->ld, count, c->d_lb, c->d_ub, c->d_sigma_init, c->d_X, c->d_work, &P, c->d_res, ext, c->st);
         /* the state in LDS while it fits there, its matrices in c->d_work beyond (nla_local_ctx_create_cobyla sized it so) */
         return (nla_cobyla_fits(c->n) || !nla_cobyla_global_serves(c->n) ? nla_k_cobyla_batch : nla_k_cobyla_batch_global)
                    (obj, c->n, c->ld, count, c->d_lb, c->d_ub, c->d_sigma_init, c->d_X, c->d_work, c->d_iwork, &P, c->d_res, c->st);

@@ -449,8 +449,11 @@ nlopt_result nla_mlsl_minimize(nlopt_opt opt, int n, nlopt_func f, void *f_data,
     /* LN_COBYLA (GN_MLSL's default, optimize.c:763-768).  With a compiled-in device objective (round 6) the searches of a batch run
      * CONCURRENTLY on the device, one wavefront per start, like LD_LBFGS / LD_MMA: `cob_dev`.  The search's whole state is in LDS while
      * it fits a compute unit's (n <= 51, hip/cobyla_kernels.hip); beyond, up to NLA_COBYLA_GLOBAL_MAX_N, its matrices are in device
-     * memory (hip/cobyla_global.hip) — the same search, lbfgs_driver.c picks the launcher.  Otherwise — a host callback, a user kernel,
-     * a dimension beyond both kernels (or a device layer without the second), or "amd_cobyla_host" = 1 — it is a HOST algorithm
+     * memory (hip/cobyla_global.hip) — the same search, lbfgs_driver.c picks the launcher.  With a user-supplied device objective
+     * (NLA_EVAL_USER) on one process, n <= NLA_COBYLA_GLOBAL_MAX_N, the same again as a coroutine (hip/cobyla_ext.hip): the waiting
+     * searches of a batch are evaluated by ONE launch of the user's kernel per step (nla_local_ctx_run), and everything behind
+     * `cob_dev` is the compiled-in case's.  Otherwise — a host callback, a user kernel on several ranks (nothing there to check it
+     * against), a dimension beyond the kernels (or a device layer without them), or "amd_cobyla_host" = 1 — it is a HOST algorithm
      * (cobyla_host.c): the searches run one at a time on the caller's thread through the library's own nlopt_optimize, exactly as
      * mlsl.c:404-407 runs them; samples, distances and the bookkeeping stay on the device, and the run takes the host-callback path
      * throughout. */
@@ -466,8 +469,9 @@ nlopt_result nla_mlsl_minimize(nlopt_opt opt, int n, nlopt_func f, void *f_data,
     }
     nla_evaluator_resolve(&D.ev, opt, f, f_data);
     D.obj = D.ev.kind == NLA_EVAL_DEVICE ? D.ev.obj : -1;
-    cob_dev = use_cobyla && D.ev.kind == NLA_EVAL_DEVICE && (nla_cobyla_fits(n) || nla_cobyla_global_serves(n)) && !(opt && nlopt_get_param(opt, "amd_cobyla_host", 0) != 0) &&
-              !nlopt_get_param(local_opt, "amd_cobyla_host", 0);
+    cob_dev = use_cobyla && ((D.ev.kind == NLA_EVAL_DEVICE && (nla_cobyla_fits(n) || nla_cobyla_global_serves(n))) ||
+                             (D.ev.kind == NLA_EVAL_USER && nla_cobyla_ext_serves(n) && nlopt_amd_comm_world(opt ? opt->comm : NULL) == 1)) &&
+              !(opt && nlopt_get_param(opt, "amd_cobyla_host", 0) != 0) && !nlopt_get_param(local_opt, "amd_cobyla_host", 0);
     /* a fixed coordinate (lb[i] == ub[i]): the reference's nlopt_optimize_limited eliminates it in front of each COBYLA search
      * (optimize.c:412-445), the device kernel does not (it refuses such a box, include/nlopt_amd.h) — the host algorithm, whose
      * nlopt_optimize eliminates like the reference (api_optimize.c fix_applies) */

@@ -263,6 +263,15 @@ static inline int nla_cobyla_global_serves(int n)
 {
     return nla_k_cobyla_batch_global && nla_cobyla_global_work_doubles && n >= 1 && n <= NLA_COBYLA_GLOBAL_MAX_N;
 }
+/* device COBYLA for a user-supplied device objective (hip/cobyla_ext.hip: the same search as a coroutine), reached the same way: a
+ * device layer without it keeps such runs on the host algorithm.  1: the launcher is there and serves n. */
+extern __typeof(nla_k_cobyla_batch_ext) nla_k_cobyla_batch_ext __attribute__((weak));
+extern __typeof(nla_cobyla_ext_work_doubles) nla_cobyla_ext_work_doubles __attribute__((weak));
+extern __typeof(nla_cobyla_save_bytes) nla_cobyla_save_bytes __attribute__((weak));
+static inline int nla_cobyla_ext_serves(int n)
+{
+    return nla_k_cobyla_batch_ext && nla_cobyla_ext_work_doubles && nla_cobyla_save_bytes && n >= 1 && n <= NLA_COBYLA_GLOBAL_MAX_N;
+}
 int nla_local_ctx_alg(const nla_local_ctx *c);
 void nla_local_ctx_destroy(nla_local_ctx *c);
 double *nla_local_ctx_X(nla_local_ctx *c);

@@ -69,8 +69,99 @@ def run(L, obj, n, starts, lo, hi, xtol_rel=1e-6, maxeval=0, ftol_rel=0.0, dx=No
     return dict(x=X[:, :n].copy(), f=np.array([r.f for r in res]), ret=[r.ret for r in res], nevals=[r.nevals for r in res])
 
 
+OUT_EXT = os.path.join(ROOT, "tools", "_build", "libcobyla_ext_emu.so")
+
+
+def build_ext():
+    """hip/cobyla_ext.hip (the same search as a coroutine around an objective outside the kernel) the same way: tests/test_cobyla_ext_emu.py"""
+    return build("cobyla_ext.hip", OUT_EXT)
+
+
+class Ext(C.Structure):
+    """nla_local_ext (include/nlopt_amd.h)"""
+    _fields_ = [("req", C.c_void_p), ("EX", C.c_void_p), ("EG", C.c_void_p), ("EF", C.c_void_p), ("save", C.c_void_p),
+                ("resume", C.c_int32), ("forced", C.c_int32), ("timeout", C.c_int32), ("pad", C.c_int32)]
+
+
+class HostMem:
+    """the buffers of run_ext in host memory (the emulated kernel); tests/test_gpu_cobyla_ext.py has the device's"""
+    class Buf:
+        def __init__(self, a):
+            self.a = a; self.ptr = a.ctypes.data
+
+    def alloc(self, nbytes, fill=0):
+        return self.Buf(np.full(max(int(nbytes), 8), fill, dtype=np.uint8))
+
+    def put(self, a):
+        return self.Buf(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy())
+
+    def write(self, buf, a):
+        buf.a[:a.nbytes] = np.ascontiguousarray(a).view(np.uint8).reshape(-1)
+
+    def read(self, buf, dtype, count):
+        return buf.a[:np.dtype(dtype).itemsize * count].view(dtype).copy()
+
+    def sync(self):
+        pass
+
+
+def ext_bind(L):
+    vp = C.c_void_p
+    L.nla_cobyla_ext_work_doubles.restype = C.c_size_t; L.nla_cobyla_ext_work_doubles.argtypes = [C.c_int, C.c_int]
+    L.nla_cobyla_save_bytes.restype = C.c_size_t; L.nla_cobyla_save_bytes.argtypes = [C.c_int]
+    L.nla_k_cobyla_batch_ext.restype = C.c_int
+    L.nla_k_cobyla_batch_ext.argtypes = [C.c_int] * 3 + [vp] * 5 + [C.POINTER(Params), vp, C.POINTER(Ext), vp]
+    return L
+
+
+def run_ext(L, n, starts, lo, hi, evaluate, xtol_rel=1e-6, maxeval=0, ftol_rel=0.0, dx=None, minf_max=-np.inf, forced_from=None, mem=None,
+            max_steps=1000000):
+    """the host side of the coroutine nla_k_cobyla_batch_ext: launch, read req, evaluate every waiting row of EX with `evaluate`
+    (the value goes into EF as it comes: the caller applies a maximisation's sign), launch again with resume = 1 until no search
+    waits.  forced_from = k: ext.forced = 1 from the k-th relaunch on (the first launch is number 0).  `asked`: per search, the
+    points it requested in order; `finished_at`: the launch after which its state was 2; `seen`: states after every launch."""
+    ext_bind(L)
+    mem = mem or HostMem()
+    count, ld = starts.shape[0], (n + 1) & ~1
+    X = np.zeros((count, ld)); X[:, :n] = starts
+    bX, bl, bu = mem.put(X), mem.put(np.asarray(lo, dtype=np.float64)), mem.put(np.asarray(hi, dtype=np.float64))
+    bd = mem.put(np.asarray(dx, dtype=np.float64)) if dx is not None else None
+    # NaN everywhere a starting search must not rely on: it zeroes its slice itself and writes its record before it reads it
+    bw = mem.alloc(8 * L.nla_cobyla_ext_work_doubles(n, count), 0xff)
+    bsave, breq = mem.alloc(L.nla_cobyla_save_bytes(n) * count, 0xff), mem.put(np.zeros((count, 2), dtype=np.int32))
+    bEX, bEG, bEF = mem.put(np.full((count, ld), np.nan)), mem.put(np.full(8, np.nan)), mem.put(np.full(count, np.nan))
+    bo = mem.alloc(C.sizeof(Result) * count)
+    P = Params(minf_max, ftol_rel, 0.0, xtol_rel, maxeval, 0, 1.0, None, None, None)
+    E = Ext(breq.ptr, bEX.ptr, bEG.ptr, bEF.ptr, bsave.ptr, 0, 0, 0, 0)
+    asked, finished_at, seen, step = [[] for _ in range(count)], [None] * count, [], 0
+    while True:
+        E.forced = 1 if forced_from is not None and step >= forced_from else 0
+        rc = L.nla_k_cobyla_batch_ext(n, ld, count, bl.ptr, bu.ptr, bd.ptr if bd else None, bX.ptr, bw.ptr, C.byref(P), bo.ptr, C.byref(E), None)
+        assert rc == 0, rc
+        mem.sync()
+        state = mem.read(breq, np.int32, 2 * count).reshape(count, 2)[:, 0]
+        seen.append(state.copy())
+        for i in range(count):
+            if state[i] == 2 and finished_at[i] is None:
+                finished_at[i] = step
+        waiting = [i for i in range(count) if state[i] == 1]
+        if not waiting:
+            break
+        assert step < max_steps
+        EX, EF = mem.read(bEX, np.float64, count * ld).reshape(count, ld), mem.read(bEF, np.float64, count)
+        for i in waiting:
+            asked[i].append(EX[i, :n].copy())
+            EF[i] = evaluate(EX[i, :n].copy())
+        mem.write(bEF, EF)
+        E.resume = 1
+        step += 1
+    res = (Result * count).from_buffer_copy(mem.read(bo, np.uint8, C.sizeof(Result) * count).tobytes())
+    return dict(x=mem.read(bX, np.float64, count * ld).reshape(count, ld)[:, :n].copy(), f=np.array([r.f for r in res]), ret=[r.ret for r in res],
+                nevals=[r.nevals for r in res], asked=asked, finished_at=finished_at, seen=seen, launches=step + 1)
+
+
 def main():
-    quick = len(sys.argv) > 1 and sys.argv[1] == "quick"
+    quick =len(sys.argv) > 1 and sys.argv[1] == "quick"
     build()
     K = C.CDLL(OUT)                                                        # the kernel on 64 lockstep CPU threads
     H = C.CDLL(os.path.join(ROOT, "oracle", "libnlopt_amd_emu.so"))        # the host algorithm
