@@ -65,6 +65,23 @@ nlopt_result nlopt_amd_set_min_device_objective(nlopt_opt opt, const char *code_
 nlopt_result nlopt_amd_set_max_device_objective(nlopt_opt opt, const char *code_object, const char *name, nlopt_func host_twin, void *f_data);
 int nlopt_amd_has_device_objective(const nlopt_opt opt);   /* 1: a user objective is bound, 0: not */
 
+/* ---- user-supplied device constraints (NLOPT_GN_ISRES evaluates them on the device) --------------------------------
+ * code_object / name: a gfx950 code object whose source describes a block of m constraint values with
+ * NLOPT_AMD_DEVICE_CONSTRAINTS(name, ...) of include/nlopt_amd_device.h; `name` selects the kernel <name>_coneval.  Each call
+ * appends ONE ordinary m-dimensional constraint, exactly as nlopt_add_inequality_mconstraint / nlopt_add_equality_mconstraint
+ * would (same algorithm check, same tolerances: tol == NULL means zeros) — except that m == 0 is refused.  host_twin (may be
+ * NULL): the same m values as an ordinary nlopt_mfunc, called with `data`; it is what every host path sees (amd_host_eval, fixed
+ * coordinates, AUGLAG, COBYLA, MMA).  Without a twin those paths send single points through the kernel (values only: no
+ * gradients).  The bound block is owned by the nlopt_opt, shared with its nlopt_copy copies (reference counted), released by
+ * nlopt_remove_*_constraints and nlopt_destroy, and never handed to the caller's nlopt_set_munge hooks (the loops over
+ * constraint data skip it).  Returns NLOPT_SUCCESS, NLOPT_INVALID_ARGS (errmsg: bad arguments, the file / symbol that could not
+ * be loaded, an ABI mismatch, or an algorithm without constraints) or NLOPT_FAILURE (no device); on failure nothing is added. */
+nlopt_result nlopt_amd_add_inequality_device_mconstraint(nlopt_opt opt, unsigned m, const char *code_object, const char *name,
+                                                         nlopt_mfunc host_twin, void *data, const double *tol);
+nlopt_result nlopt_amd_add_equality_device_mconstraint(nlopt_opt opt, unsigned m, const char *code_object, const char *name,
+                                                       nlopt_mfunc host_twin, void *data, const double *tol);
+int nlopt_amd_device_constraint_count(const nlopt_opt opt);   /* bound blocks, inequality + equality */
+
 /* per-evaluation trace (same record as the oracle's): kind 0 = initial row, 1 = reflection trial,
  * 2 = local mutation; row = row written (init / accepted) or -1. */
 typedef struct { double f; int64_t row; int32_t kind; int32_t accepted; } nlopt_amd_trace_rec;
@@ -126,6 +143,9 @@ typedef struct {
     /* MLSL: gates in front of the sampling phase enqueued ahead that gave up waiting (50 ms) for the searches they start behind — the two
      * streams did not run beside each other; the run stops gating after the first.  0 in a healthy run */
     uint64_t mlsl_gate_timeouts;
+    /* ISRES: launches of users' constraint kernels (<name>_coneval; one per bound block and generation).  0: the constraints of the
+     * run were block sums, or were called on the host */
+    uint64_t isres_usercon_launches;
 } nlopt_amd_stats;
 nlopt_result nlopt_amd_get_stats(const nlopt_opt opt, nlopt_amd_stats *out);
 /* ... for a client that may have been built against an older or newer header: writes at most `bytes` bytes of the structure (fields are
@@ -403,7 +423,8 @@ int nla_k_crs_mutate(int n, const double *best, double *p, const uint32_t *words
 /* ---- ISRES (src/algs/isres/isres.c) --------------------------------------------------------------
  * X, S (step sizes): pop x ld fp64 row-major; F/PEN/GPEN: pop fp64; FEAS: pop i32. */
 
-/* a constraint the device can evaluate; type 0 = block sum  sum_{i in block q of Q} x_i - 1 */
+/* a constraint the device can evaluate; type 0 = block sum  sum_{i in block q of Q} x_i - 1; type 1 = value already computed:
+ * q is the column of the candidate's row of C (nla_k_isres_eval_cv) that holds it, Q and pad are unused */
 typedef struct { int32_t type; uint32_t q, Q; int32_t pad; double tol; } nla_dev_constraint;
 
 /* replaces: the initial population, isres.c:122-128, for individuals k_first .. k_first+count-1
@@ -418,6 +439,11 @@ int nla_k_isres_init(int n, int ld, const double *lb, const double *ub, const ui
  * objective is a user-supplied kernel, nlopt_amd_set_min_device_objective). */
 int nla_k_isres_eval(int obj, int n, int ld, const double *X, int64_t pop, int m, int p, const nla_dev_constraint *con,
                      double *F, double *PEN, double *GPEN, int32_t *FEAS, void *stream);
+/* the same with constraint values computed beforehand (a user's <name>_coneval kernels): an entry of type 1 takes its value from
+ * C[k * ldc + q] (k = the candidate's row in X) instead of computing a block sum; types 0 and 1 may be interleaved in any order.
+ * m and p count scalar entries.  C == NULL: nla_k_isres_eval (an entry of type 1 then has the value NaN). */
+int nla_k_isres_eval_cv(int obj, int n, int ld, const double *X, int64_t pop, int m, int p, const nla_dev_constraint *con,
+                        const double *C, int ldc, double *F, double *PEN, double *GPEN, int32_t *FEAS, void *stream);
 
 /* replaces: nlopt_qsort_r(irank, ..., fval, key_compare), isres.c:204 (sorted[pos] = individual,
  * stable), and prepares the stochastic ranking: elems[k] = individual k packed with the dense ranks

@@ -78,7 +78,42 @@ __device__ __forceinline__ void evalgrad_kernel_body(int n, int ld, long count, 
     evalgrad_wave<OBJ>(n, X + row * (long) ld, F + row, wantg ? G + row * (long) ld : nullptr, sign);
 }
 
+/* ---- nonlinear constraints (NLOPT_GN_ISRES; bound with nlopt_amd_add_inequality_device_mconstraint /
+ * nlopt_amd_add_equality_device_mconstraint of include/nlopt_amd.h) ----------------------------------------------------------
+ * A block of m constraints is described by its values:
+ *
+ *   struct MyCons {
+ *       // value of constraint j (0 <= j < m) at x; plain sequential C++, called by ONE lane
+ *       __device__ static double value(int n, int j, const double *x);
+ *   };
+ *   NLOPT_AMD_DEVICE_CONSTRAINTS(mycons, MyCons)
+ *
+ * Contract: one wavefront takes one candidate; lane j % 64 evaluates constraint j, alone and in program order (no reduction
+ * across lanes).  A host twin written from the same formulas and compiled with -ffp-contract=off therefore gives the same bits as
+ * long as the formulas use + - * / and sqrt only; the device's and the host's libm transcendentals (exp, sin, pow, ...) may differ
+ * in the last places.
+ *
+ * Kernel ABI (<name>_coneval, 64 x 4 threads per workgroup, one wavefront per candidate):
+ *   (int n, int ld, long count, const double *X, int m, int ldc, double *C)
+ *   C[row * ldc + j] = value(n, j, X + row * ld) for row < count, j < m.  <name>_conabi(int *out) writes the ABI version; it is
+ *   separate from <name>_abi, so one code object may hold an objective and a constraint block under the same name. */
+template <class CON>
+__device__ __forceinline__ void coneval_kernel_body(int n, int ld, long count, const double *X, int m, int ldc, double *C)
+{
+    const int lane = threadIdx.x & 63;
+    const long row = (long) blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (row >= count) return;
+    const double *x = X + row * (long) ld;
+    for (int j = lane; j < m; j += 64) C[row * (long) ldc + j] = CON::value(n, j, x);
+}
+
 }  // namespace nlopt_amd_device
+
+#define NLOPT_AMD_DEVICE_CONSTRAINTS(name, CON)                                                                                \
+    extern "C" __global__ __launch_bounds__(256) void name##_coneval(int n, int ld, long count, const double *X, int m,        \
+                                                                     int ldc, double *C)                                       \
+    { nlopt_amd_device::coneval_kernel_body<CON>(n, ld, count, X, m, ldc, C); }                                                \
+    extern "C" __global__ void name##_conabi(int *out) { *out = NLOPT_AMD_DEVICE_ABI; }
 
 #define NLOPT_AMD_DEVICE_OBJECTIVE(name, OBJ)                                                                                  \
     extern "C" __global__ __launch_bounds__(256) void name##_evalgrad(int n, int ld, long count, const int *list,              \

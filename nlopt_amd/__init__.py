@@ -26,6 +26,7 @@ SUCCESS, STOPVAL_REACHED, FTOL_REACHED, XTOL_REACHED, MAXEVAL_REACHED, MAXTIME_R
 OBJECTIVES = {"rastrigin": 0, "ackley": 1, "griewank": 2, "rosenbrock": 3, "levy": 4, "sphere": 5}
 
 NLOPT_FUNC = C.CFUNCTYPE(C.c_double, C.c_uint, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_void_p)
+NLOPT_MFUNC = C.CFUNCTYPE(None, C.c_uint, C.POINTER(C.c_double), C.c_uint, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_void_p)
 
 TRACE_DTYPE = np.dtype([("f", "f8"), ("row", "i8"), ("kind", "i4"), ("accepted", "i4")])
 
@@ -43,7 +44,8 @@ class Stats(C.Structure):
                 ("evolve_rounds_enqueued", C.c_uint64), ("evolve_rounds", C.c_uint64),
                 ("t_engine_s", C.c_double), ("t_walk_s", C.c_double),
                 ("list_refreshes", C.c_uint64), ("list_refreshes_beside_device", C.c_uint64), ("t_list_refresh_s", C.c_double),
-                ("isres_gate_timeouts", C.c_uint64), ("mlsl_sampled_ahead", C.c_uint64), ("cobyla_host_searches", C.c_uint64), ("lbfgs_longest_chain_steps", C.c_uint64), ("mlsl_gate_timeouts", C.c_uint64)]
+                ("isres_gate_timeouts", C.c_uint64), ("mlsl_sampled_ahead", C.c_uint64), ("cobyla_host_searches", C.c_uint64), ("lbfgs_longest_chain_steps", C.c_uint64), ("mlsl_gate_timeouts", C.c_uint64),
+                ("isres_usercon_launches", C.c_uint64)]
 
     def asdict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -187,6 +189,11 @@ def lib():
     L.nla_k_crs_advance.argtypes = [C.c_int, C.c_int, vp, C.c_int64, vp, vp, vp, C.c_uint32, C.c_uint64, C.c_int, vp, C.c_int,
                                     vp, vp, C.c_int, vp, vp, vp, C.c_int, vp]
     L.nlopt_amd_has_device_objective.argtypes = [vp]
+    for nm in ("nlopt_amd_add_inequality_device_mconstraint", "nlopt_amd_add_equality_device_mconstraint"):
+        getattr(L, nm).argtypes = [vp, C.c_uint, C.c_char_p, C.c_char_p, vp, vp, dpp]
+    L.nlopt_amd_device_constraint_count.argtypes = [vp]
+    if hasattr(L, "nla_k_isres_eval_cv"):       # (not in the emulated device layer: no code object loads there, so nothing needs it)
+        L.nla_k_isres_eval_cv.argtypes = [C.c_int, C.c_int, C.c_int, vp, C.c_int64, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp, vp, vp, vp]
     L.nla_dev_malloc_uncached.argtypes = [C.c_size_t]
     L.nla_dev_malloc_uncached.restype = vp
     L.nla_dev_free_uncached.argtypes = [vp]
@@ -530,6 +537,35 @@ class Opt:
         for q in range(count):
             data[2 * q], data[2 * q + 1] = q, count
             self._ck(add(self._h, cb, C.addressof(data) + 8 * q, float(tol)))
+
+    def _add_device_constraints(self, equality, code_object, name, m, host_twin, tol):
+        fn = self._L.nlopt_amd_add_equality_device_mconstraint if equality else self._L.nlopt_amd_add_inequality_device_mconstraint
+        twin = None
+        if host_twin is not None:
+            def _cb(mm, res, n, x, g, d):
+                v = host_twin(np.ctypeslib.as_array(x, shape=(n,)))
+                for j in range(mm):
+                    res[j] = float(v[j])
+            cb = NLOPT_MFUNC(_cb)
+            self._keep.append(cb)
+            twin = C.cast(cb, C.c_void_p).value
+        t = None
+        if tol is not None:
+            t = np.ascontiguousarray(np.broadcast_to(np.asarray(tol, dtype=np.float64), (int(m),)))
+        return fn(self._h, int(m), code_object.encode() if code_object is not None else None, name.encode() if name is not None else None,
+                  twin, None, _dp(t) if t is not None else None)
+
+    def add_inequality_device_constraints(self, code_object, name, m, host_twin=None, tol=None):
+        """bind a block of m user-supplied device constraints g_j(x) <= 0 (include/nlopt_amd_device.h): kernel <name>_coneval of the
+        code object; host_twin(x) -> sequence of m values is what the host paths call; tol: scalar or m tolerances (None: zeros)"""
+        return self._add_device_constraints(False, code_object, name, m, host_twin, tol)
+
+    def add_equality_device_constraints(self, code_object, name, m, host_twin=None, tol=None):
+        """... the same as equality constraints h_j(x) == 0"""
+        return self._add_device_constraints(True, code_object, name, m, host_twin, tol)
+
+    def device_constraint_count(self):
+        return self._L.nlopt_amd_device_constraint_count(self._h)
 
     # -- stopping criteria & parameters --
     def set_stopval(self, v): self._ck(self._L.nlopt_set_stopval(self._h, float(v)))

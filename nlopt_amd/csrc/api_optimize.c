@@ -251,11 +251,13 @@ static nlopt_result minimize_fixed_eliminated(nlopt_opt opt, double *x, double *
     for (i = 0; i < opt->m; ++i) {
         fixdim *d = &dd[1 + i];
         d->f = opt->fc[i].f; d->mf = opt->fc[i].mf; d->f_data = opt->fc[i].f_data;
+        nla_usercon_release(nla_usercon_of(r->fc + i));       /* (the copy's reference to a user device block: opt keeps its own for the run) */
         r->fc[i].f = opt->fc[i].f ? fix_func : NULL; r->fc[i].mf = opt->fc[i].mf ? fix_mfunc : NULL; r->fc[i].f_data = d;
     }
     for (i = 0; i < opt->p; ++i) {
         fixdim *d = &dd[1 + opt->m + i];
         d->f = opt->h[i].f; d->mf = opt->h[i].mf; d->f_data = opt->h[i].f_data;
+        nla_usercon_release(nla_usercon_of(r->h + i));
         r->h[i].f = opt->h[i].f ? fix_func : NULL; r->h[i].mf = opt->h[i].mf ? fix_mfunc : NULL; r->h[i].f_data = d;
     }
     r->trace = opt->trace; r->trace_cap = opt->trace_cap; r->progress = opt->progress; r->progress_data = opt->progress_data;
@@ -296,7 +298,8 @@ static double best_seen_objective(unsigned n, const double *x, double *grad, voi
  * callback like any other objective?  "On the device" only where the driver really evaluates every point there:
  *   LD_LBFGS, MLSL*: always;  LD_MMA: without nonlinear constraints (with them the outer algorithm calls f on the host, mma_host.c);
  *   CRS2_LM / ESCH: unless amd_host_eval or fixed coordinates (the elimination wrapper) put a host function in front;
- *   ISRES: additionally only if every constraint is a device constraint (isres_driver.c falls back to host calls otherwise). */
+ *   ISRES: additionally only if every constraint is a device constraint — a block sum or a user's bound constraint kernel
+ *   (isres_driver.c falls back to host calls otherwise). */
 static int objective_stays_on_device(const nlopt_opt opt)
 {
     const nlopt_algorithm a = opt->algorithm;

@@ -55,6 +55,8 @@ __global__ __launch_bounds__(256) void isres_init_kernel(int n, int ld, const do
  * in the reference's sequential order (so the penalties are bit-identical to the host callbacks),
  * combined in constraint order: inequalities (gval > tol -> infeasible, max(g,0)^2), the
  * inequality-only snapshot gpenalty, then equalities (|h| > tol -> infeasible, h^2).
+ * A constraint of type 1 has been computed already (a user's <name>_coneval kernel, userobj.c's sibling usercon.c): its value
+ * is column q of the candidate's row of C (pop x ldc); the fold is the same.
  * ---------------------------------------------------------------------------------------------- */
 __device__ __forceinline__ double isres_constraint_value(const nla_dev_constraint &c, int n, const double *x)
 {
@@ -69,7 +71,8 @@ __device__ __forceinline__ double isres_constraint_value(const nla_dev_constrain
 template <int OBJ>
 __global__ __launch_bounds__(256) void isres_eval_kernel(int n, int ld, const double *__restrict__ X, int64_t pop, int m, int p,
                                                           const nla_dev_constraint *__restrict__ con, double *__restrict__ F,
-                                                          double *__restrict__ PEN, double *__restrict__ GPEN, int32_t *__restrict__ FEAS, double sign)
+                                                          double *__restrict__ PEN, double *__restrict__ GPEN, int32_t *__restrict__ FEAS, double sign,
+                                                          const double *__restrict__ C, int ldc)
 {
     const int lane = threadIdx.x & 63;
     const int64_t k = (int64_t) blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -82,8 +85,13 @@ __global__ __launch_bounds__(256) void isres_eval_kernel(int n, int ld, const do
     const int mp = m + p;
     for (int c0 = 0; c0 < mp; c0 += 64) {
         const int c = c0 + lane;
-        const double v = (c < mp) ? isres_constraint_value(con[c], n, x) : 0.0;
-        const double tol = (c < mp) ? con[c].tol : 0.0;
+        double v = 0.0, tol = 0.0;
+        if (c < mp) {
+            const nla_dev_constraint cc = con[c];
+            tol = cc.tol;
+            if (cc.type == NLA_CON_VALUE) v = C ? C[(size_t) k * (size_t) ldc + cc.q] : __builtin_nan("");   /* (no values given: NaN, not a block sum with Q = 0) */
+            else v = isres_constraint_value(cc, n, x);
+        }
         const int cnt = mp - c0 < 64 ? mp - c0 : 64;
         for (int u = 0; u < cnt; ++u) {                 /* in constraint order, every lane the same chain */
             double g = __shfl(v, u, 64);
@@ -685,19 +693,26 @@ extern "C" int nla_k_isres_init(int n, int ld, const double *lb, const double *u
     return 0;
 }
 
-extern "C" int nla_k_isres_eval(int obj, int n, int ld, const double *X, int64_t pop, int m, int p, const nla_dev_constraint *con,
-                                double *F, double *PEN, double *GPEN, int32_t *FEAS, void *stream)
+/* C == NULL: every entry is a block sum (nla_k_isres_eval) */
+extern "C" int nla_k_isres_eval_cv(int obj, int n, int ld, const double *X, int64_t pop, int m, int p, const nla_dev_constraint *con,
+                                   const double *C, int ldc, double *F, double *PEN, double *GPEN, int32_t *FEAS, void *stream)
 {
     if (pop <= 0) return 0;
     const dim3 grid((unsigned) ((pop + 3) / 4)), block(256);
     hipStream_t st = (hipStream_t) stream;
     const double sign = nla_obj_sign(&obj);
-#define CALL(O) hipLaunchKernelGGL((isres_eval_kernel<O>), grid, block, 0, st, n, ld, X, pop, m, p, con, F, PEN, GPEN, FEAS, sign)
+#define CALL(O) hipLaunchKernelGGL((isres_eval_kernel<O>), grid, block, 0, st, n, ld, X, pop, m, p, con, F, PEN, GPEN, FEAS, sign, C, ldc)
     if (obj < 0) { CALL(-1); }                 /* constraints only: f by a user-supplied kernel (userobj.c) */
     else NLA_OBJ_DISPATCH(obj, CALL)
 #undef CALL
     NLA_LAUNCH_CHECK();
     return 0;
+}
+
+extern "C" int nla_k_isres_eval(int obj, int n, int ld, const double *X, int64_t pop, int m, int p, const nla_dev_constraint *con,
+                                double *F, double *PEN, double *GPEN, int32_t *FEAS, void *stream)
+{
+    return nla_k_isres_eval_cv(obj, n, ld, X, pop, m, p, con, NULL, 0, F, PEN, GPEN, FEAS, stream);
 }
 
 extern "C" int nla_k_isres_rank_count(int64_t pop, const double *F, const double *PEN, uint64_t *elems, int32_t *sorted, void *stream)

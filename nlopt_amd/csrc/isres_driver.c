@@ -70,6 +70,11 @@ typedef struct {
     int64_t *d_zatt, *d_ztotal, *d_state;
     uint32_t *d_words;
     nla_dev_constraint *d_con;
+    /* D.m / D.p count nla_constraint entries (what the host loop walks); sm / sp count SCALAR entries (what the evaluation kernel folds: an
+     * m-dimensional block of a user's constraint kernel contributes m of them) */
+    int sm, sp;
+    int nblk; nla_usercon **blk; int *blk_col;   /* users' constraint kernels (usercon.c) in the order added, and the first column of each in d_C */
+    int ldc; double *d_C;                        /* their values: pop x ldc, block b in columns [blk_col[b], blk_col[b] + its m); only when nblk > 0 */
     int64_t zcap;
     double *h_F, *h_PEN, *h_GPEN, *h_X;
     int32_t *h_FEAS;
@@ -90,7 +95,7 @@ static void dev_free_all(isres_dev *d)
     nla_dev_free(d->d_PEN); nla_dev_free(d->d_GPEN); nla_dev_free(d->d_scratch); nla_dev_free(d->d_z); nla_dev_free(d->d_FEAS);
     nla_dev_free(d->d_irank); nla_dev_free(d->d_counts); nla_dev_free(d->d_progress); nla_dev_free(d->d_ticket);
     nla_dev_free(d->d_swapped); nla_dev_free(d->d_streams); nla_dev_free(d->d_bits); nla_dev_free(d->d_zatt); nla_dev_free(d->d_gate);
-    nla_dev_free(d->d_ztotal); nla_dev_free(d->d_state); nla_dev_free(d->d_words); nla_dev_free(d->d_con);
+    nla_dev_free(d->d_ztotal); nla_dev_free(d->d_state); nla_dev_free(d->d_words); nla_dev_free(d->d_con); nla_dev_free(d->d_C);
     nla_dev_free(d->d_inv); nla_dev_free(d->d_rho); nla_dev_free(d->d_ws); nla_dev_free(d->d_mu);
     nla_host_free(d->h_F); nla_host_free(d->h_PEN); nla_host_free(d->h_GPEN); nla_host_free(d->h_X); nla_host_free(d->h_FEAS);
     nla_host_free(d->h_swapped); nla_host_free(d->h_progress);
@@ -146,7 +151,8 @@ static int dev_alloc(isres_dev *d, const double *lb, const double *ub, const nla
     A(d_swapped, uint8_t, pop); A(d_bits, uint64_t, d->m + d->p > 0 ? (size_t) d->popcap * (size_t) d->rowwords : 1);      /* (equal blocks of `per` rows for the all-gather) */
     A(d_words, uint32_t, d->wchunk); A(d_z, double, d->zcap); A(d_zatt, int64_t, d->zcap);
     A(d_counts, int32_t, d->wchunk / 4 / 1024 + 16); A(d_ztotal, int64_t, 1); A(d_state, int64_t, 16);
-    A(d_con, nla_dev_constraint, d->m + d->p + 1);
+    A(d_con, nla_dev_constraint, d->sm + d->sp + 1);
+    if (d->nblk > 0) A(d_C, double, pop * (size_t) d->ldc);
     A(d_gate, int, d->units + 3);
     d->ev_gate = nla_event_create();
     if (!d->ev_gate) ok = 0;
@@ -166,7 +172,7 @@ static int dev_alloc(isres_dev *d, const double *lb, const double *ub, const nla
     d->h_X = (double *) nla_host_malloc(sizeof(double) * (d->dev_eval ? n : pop * ld));
     if (!ok || !d->h_F || !d->h_PEN || !d->h_GPEN || !d->h_FEAS || !d->h_swapped || !d->h_progress || !d->h_X) return -1;
     if (nla_memcpy_h2d(d->d_lb, lb, sizeof(double) * n, d->st) || nla_memcpy_h2d(d->d_ub, ub, sizeof(double) * n, d->st)) return -1;
-    if (d->m + d->p > 0 && d->dev_eval && nla_memcpy_h2d(d->d_con, con, sizeof(nla_dev_constraint) * (size_t) (d->m + d->p), d->st)) return -1;
+    if (d->sm + d->sp > 0 && d->dev_eval && nla_memcpy_h2d(d->d_con, con, sizeof(nla_dev_constraint) * (size_t) (d->sm + d->sp), d->st)) return -1;
     d->h_progress[0] = (int) d->pop;
     for (int64_t u = 1; u <= d->units; ++u) d->h_progress[u] = 0;
     return nla_stream_sync(d->st) ? -1 : 0;
@@ -494,11 +500,16 @@ static int con_eval_host(const nla_constraint *c, unsigned n, const double *x, d
     return 0;
 }
 
-/* a constraint the evaluation kernel can compute: the registered block-sum constraint with valid data */
-static int device_constraint(const nla_constraint *cc)
+/* a constraint the evaluation kernel can compute itself: the registered block-sum constraint with valid data */
+static int blocksum_constraint(const nla_constraint *cc)
 {
     const unsigned *qQ = (const unsigned *) cc->f_data;
     return cc->f && cc->m == 1 && nlopt_amd_constraint_id(cc->f) == NLA_CON_BLOCKSUM && qQ && qQ[1] != 0 && qQ[0] < qQ[1];
+}
+/* ... or one whose values a user's bound constraint kernel computes on the device (usercon.c) and the evaluation kernel folds */
+static int device_constraint(const nla_constraint *cc)
+{
+    return blocksum_constraint(cc) || (nla_usercon_of(cc) != NULL && nla_k_isres_eval_cv != NULL);
 }
 /* will a run with these constraints evaluate everything on the device (given a device objective)?  The dispatcher asks before it
  * decides who negates a maximised objective (api_optimize.c). */
@@ -519,8 +530,8 @@ nlopt_result nla_isres_minimize(nlopt_opt opt, int n, nlopt_func f, void *f_data
     nla_dev_constraint *con = NULL;
     nlopt_amd_stats *st = opt ? &opt->stats : NULL;
     double minf_penalty = HUGE_VAL, minf_gpenalty = HUGE_VAL, taup, tau, *results = NULL;
-    unsigned maxdim = 1;
-    int j, c, dev_eval, agreed_force = 0;
+    unsigned maxdim = 1, ires;
+    int j, c, e, sm = 0, sp = 0, ncols = 0, dev_eval, agreed_force = 0;
     const int need_x = stop->xtol_rel > 0 || stop->xtol_abs != NULL;
     int64_t k;
 
@@ -549,20 +560,39 @@ nlopt_result nla_isres_minimize(nlopt_opt opt, int n, nlopt_func f, void *f_data
     nla_evaluator_resolve(&D.ev, opt, f, f_data);
     D.obj = D.ev.kind == NLA_EVAL_DEVICE ? D.ev.obj : -1;
     dev_eval = D.ev.kind != NLA_EVAL_HOST && !(opt && nlopt_get_param(opt, "amd_host_eval", 0) != 0);
-    con = (nla_dev_constraint *) calloc((size_t) (m + p + 1), sizeof *con);
-    if (!con) { nla_stop_msg(stop, "nlopt_amd: out of memory"); nla_comm_agree_ready(opt ? opt->comm : NULL, 0); return NLOPT_OUT_OF_MEMORY; }
-    for (c = 0; c < m + p; ++c) {
+    for (c = 0; c < m; ++c) sm += (int) fc[c].m;
+    for (c = 0; c < p; ++c) sp += (int) h[c].m;
+    con = (nla_dev_constraint *) calloc((size_t) (sm + sp + 1), sizeof *con);
+    D.blk = (nla_usercon **) calloc((size_t) (m + p + 1), sizeof *D.blk);
+    D.blk_col = (int *) calloc((size_t) (m + p + 1), sizeof *D.blk_col);
+    if (!con || !D.blk || !D.blk_col) {
+        nla_stop_msg(stop, "nlopt_amd: out of memory"); free(con); free(D.blk); free(D.blk_col);
+        nla_comm_agree_ready(opt ? opt->comm : NULL, 0); return NLOPT_OUT_OF_MEMORY;
+    }
+    /* the scalar entries the kernel folds, in the order the caller added the constraints (isres.c:141-166): one per block sum, cc->m per
+     * user block — those with consecutive columns of the candidate's row of d_C */
+    for (c = 0, e = 0; c < m + p; ++c) {
         const nla_constraint *cc = c < m ? fc + c : h + (c - m);
         if (cc->m > maxdim) maxdim = cc->m;
-        if (device_constraint(cc)) {
+        if (blocksum_constraint(cc)) {
             const unsigned *qQ = (const unsigned *) cc->f_data;
-            con[c].type = NLA_CON_BLOCKSUM; con[c].q = qQ[0]; con[c].Q = qQ[1]; con[c].tol = cc->tol[0];
+            con[e].type = NLA_CON_BLOCKSUM; con[e].q = qQ[0]; con[e].Q = qQ[1]; con[e].tol = cc->tol[0];
+        } else if (device_constraint(cc)) {
+            D.blk[D.nblk] = nla_usercon_of(cc); D.blk_col[D.nblk++] = ncols;
+            for (ires = 0; ires < cc->m; ++ires) { con[e + ires].type = NLA_CON_VALUE; con[e + ires].q = (uint32_t) (ncols + (int) ires); con[e + ires].tol = cc->tol[ires]; }
+            ncols += (int) cc->m;
         } else dev_eval = 0;
+        e += (int) cc->m;
     }
+    if (!dev_eval) D.nblk = 0;
     results = (double *) malloc(sizeof(double) * maxdim);
-    if (!results) { nla_stop_msg(stop, "nlopt_amd: out of memory"); free(con); nla_comm_agree_ready(opt ? opt->comm : NULL, 0); return NLOPT_OUT_OF_MEMORY; }
+    if (!results) {
+        nla_stop_msg(stop, "nlopt_amd: out of memory"); free(con); free(D.blk); free(D.blk_col);
+        nla_comm_agree_ready(opt ? opt->comm : NULL, 0); return NLOPT_OUT_OF_MEMORY;
+    }
 
-    D.n = n; D.ld = (n + 1) & ~1; D.m = m; D.p = p; D.pop = population; D.dev_eval = dev_eval;
+    D.n = n; D.ld = (n + 1) & ~1; D.m = m; D.p = p; D.sm = sm; D.sp = sp; D.pop = population; D.dev_eval = dev_eval;
+    D.ldc = (ncols + 1) & ~1;
     D.comm = opt ? opt->comm : NULL;
     D.evolve_serial = opt ? nlopt_get_param(opt, "amd_isres_evolve_serial", 0) != 0 : 0;
     D.gated = 1;                     /* (A/B switches in round 5, profiles/r05_isres_steps.txt: gated 49.5 ms per generation, not gated 55.3) */
@@ -578,7 +608,7 @@ nlopt_result nla_isres_minimize(nlopt_opt opt, int n, nlopt_func f, void *f_data
             if (!mine) nla_stop_msg(stop, "nlopt_amd: could not create the ISRES device state (out of device memory?)");
             else if (all < 0) nla_stop_msg(stop, NLA_MSG_RANKS_DIFFER);
             else nla_stop_msg(stop, "nlopt_amd: another rank could not set up its ISRES device state");
-            dev_free_all(&D); free(con); free(results);
+            dev_free_all(&D); free(con); free(results); free(D.blk); free(D.blk_col);
             return !mine ? NLOPT_OUT_OF_MEMORY : (all < 0 ? NLOPT_INVALID_ARGS : NLOPT_FAILURE);
         }
     }
@@ -597,8 +627,20 @@ nlopt_result nla_isres_minimize(nlopt_opt opt, int n, nlopt_func f, void *f_data
             /* this rank's block of candidates, then the all-gather (in place: block r sits at r * per) */
             const int64_t first = D.per * nlopt_amd_comm_rank(D.comm);
             const int64_t mine = first >= D.pop ? 0 : (D.pop - first < D.per ? D.pop - first : D.per);
-            if (nla_k_isres_eval((D.obj >= 0 && D.ev.sign < 0) ? (D.obj | NLA_OBJ_NEGATE) : D.obj, n, D.ld, D.d_X + (size_t) first * (size_t) D.ld, mine, m, p, D.d_con, D.d_F + first, D.d_PEN + first,
-                                 D.d_GPEN + first, D.d_FEAS + first, D.st) ||
+            const int eobj = (D.obj >= 0 && D.ev.sign < 0) ? (D.obj | NLA_OBJ_NEGATE) : D.obj;
+            const double *Xmine = D.d_X + (size_t) first * (size_t) D.ld;
+            double *Cmine = D.nblk > 0 ? D.d_C + (size_t) first * (size_t) D.ldc : NULL;
+            int bad = 0, b;
+            /* the users' constraint kernels, one launch per block into its columns; then the fold (and the compiled-in objective) */
+            for (b = 0; b < D.nblk && !bad && mine > 0; ++b) {
+                bad = nla_usercon_eval_rows(D.blk[b], n, D.ld, mine, Xmine, D.ldc, Cmine + D.blk_col[b], D.st);
+                if (st) ++st->isres_usercon_launches;
+            }
+            if (bad ||
+                (D.nblk > 0 ? nla_k_isres_eval_cv(eobj, n, D.ld, Xmine, mine, D.sm, D.sp, D.d_con, Cmine, D.ldc, D.d_F + first, D.d_PEN + first,
+                                                  D.d_GPEN + first, D.d_FEAS + first, D.st)
+                            : nla_k_isres_eval(eobj, n, D.ld, Xmine, mine, D.sm, D.sp, D.d_con, D.d_F + first, D.d_PEN + first,
+                                               D.d_GPEN + first, D.d_FEAS + first, D.st)) ||
                 (D.ev.kind == NLA_EVAL_USER && nla_userobj_eval_rows(D.ev.user, n, D.ld, mine, D.d_X + (size_t) first * (size_t) D.ld, D.d_F + first,
                                                                       NULL, D.ev.sign, D.st)) ||
                 nla_comm_allgather_dev(D.comm, D.d_F + first, D.d_F, sizeof(double) * (size_t) D.per, D.st) ||
@@ -637,7 +679,6 @@ nlopt_result nla_isres_minimize(nlopt_opt opt, int n, nlopt_func f, void *f_data
             ++*stop->nevals_p;
             if (dev_eval) { fk = D.h_F[k]; pk = D.h_PEN[k]; gpenalty = D.h_GPEN[k]; feasible = D.h_FEAS[k]; }
             else {
-                unsigned ires;
                 xk = D.h_X + (size_t) k * (size_t) D.ld;
                 fk = f((unsigned) n, xk, NULL, f_data);
                 if (nla_stop_forced(stop)) { ret = NLOPT_FORCED_STOP; goto done; }
@@ -728,5 +769,6 @@ done:
     dev_free_all(&D);
     free(con);
     free(results);
+    free(D.blk); free(D.blk_col);
     return ret;
 }

@@ -111,6 +111,18 @@ int nla_userobj_eval_rows(nla_userobj *u, int n, int ld, int64_t count, const do
 int nla_userobj_evalgrad_list(nla_userobj *u, int n, int ld, int m, const int32_t *d_list, const double *X, double *F, double *G,
                               double sign, void *stream);
 
+/* user device constraints (usercon.c): a constraint entry whose mf is usercon.c's adapter owns one reference to the block in f_data */
+typedef struct nla_usercon nla_usercon;
+nla_usercon *nla_usercon_retain(nla_usercon *u);
+void nla_usercon_release(nla_usercon *u);
+int nla_usercon_is_adapter(nlopt_mfunc mf);
+nla_usercon *nla_usercon_of(const nla_constraint *c);       /* the block behind an adapter-owned entry, else NULL */
+/* one constraint entry of opt at one point, through the entry's own callback: the values every host path gets (the kernel-level tests
+ * read a bound block's single-point path with it) */
+int nla_constraint_eval(const nlopt_opt opt, int equality, unsigned index, unsigned n, const double *x, double *result);
+/* C[row * ldc + j] = value j of the block at row `row` of X (rows ld apart), row < count, j < the block's m */
+int nla_usercon_eval_rows(nla_usercon *u, int n, int ld, int64_t count, const double *X, int ldc, double *C, void *stream);
+
 const char *nla_set_errmsg(nlopt_opt opt, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
 void nla_unset_errmsg(nlopt_opt opt);
 char *nla_vsprintf(char *p, const char *fmt, __builtin_va_list ap);
@@ -240,6 +252,11 @@ nlopt_result nla_crs_advance(nla_crs_session *S, int64_t eval_budget);
 nlopt_result nla_crs_end(nla_crs_session *S, uint64_t *words_used);
 nlopt_result nla_crs_run(const nla_crs_engine_ops *ops, void *engine, const nla_crs_problem *pb,
                          double *x, double *minf, uint64_t *words_used);
+
+/* ISRES with users' constraint kernels: the evaluation launcher that folds precomputed values (hip/isres_kernels.hip), reached
+ * through a WEAK reference like the COBYLA launchers below — the emulated device layer links without it; there no code object
+ * loads, so no block can be bound and the launcher is never needed. */
+extern __typeof(nla_k_isres_eval_cv) nla_k_isres_eval_cv __attribute__((weak));
 
 /* reference-shaped entry (src/algs/isres/isres.h:34-41) */
 int nla_isres_constraints_on_device(unsigned m, const nla_constraint *fc, unsigned p, const nla_constraint *h);

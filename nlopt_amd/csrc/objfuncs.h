@@ -34,6 +34,7 @@
 
 /* constraint ids */
 #define NLA_CON_BLOCKSUM   0   /* g_q(x) = sum_{i in block q of Q} x_i - 1 <= 0 */
+#define NLA_CON_VALUE      1   /* already computed (a user's constraint kernel): column q of the candidate's row of values */
 
 /* sin / cos as the objectives call them.  On the host they go through functions the optimiser cannot look into: glibc's
  * sincos() and cos() (or sin()) round differently for some arguments (glibc 2.35: cos(2 pi 0.5939350286162490) differs in the
