@@ -64,6 +64,19 @@ int nlopt_amd_device_count(void);                      /* visible HIP devices (0
 nlopt_result nlopt_amd_set_min_device_objective(nlopt_opt opt, const char *code_object, const char *name, nlopt_func host_twin, void *f_data);
 nlopt_result nlopt_amd_set_max_device_objective(nlopt_opt opt, const char *code_object, const char *name, nlopt_func host_twin, void *f_data);
 int nlopt_amd_has_device_objective(const nlopt_opt opt);   /* 1: a user objective is bound, 0: not */
+/* Data for a bound ABI-2 objective (NLOPT_AMD_DEVICE_OBJECTIVE_DATA / NLOPT_AMD_DEVICE_RESIDUALS of nlopt_amd_device.h; kernel
+ * <name>_evalgrad_d): `bytes` bytes are copied AT THE CALL into device memory the library owns (the caller may free its buffer), and
+ * every launch of the kernel for this optimiser — populations, samples, local-search steps, single points — gets (pointer, bytes).
+ * The block is immutable, reference counted and belongs to the nlopt_opt, not to the loaded code object: nlopt_copy shares it, and
+ * setting data on a copy replaces that copy's block only (per-thread copies fitting different data sets share one loaded kernel).
+ * bytes == 0 clears it (the kernel then gets NULL, 0); nlopt_set_min/max_objective and nlopt_destroy release it.  The host twin
+ * does not see the block: it keeps the f_data it was bound with.  NLOPT_INVALID_ARGS with an errmsg, the optimiser unchanged: no
+ * device objective bound; the bound one is ABI 1; data == NULL with bytes > 0.  Every rank of a multi-GPU run sets the same data. */
+nlopt_result nlopt_amd_set_device_objective_data(nlopt_opt opt, const void *data, size_t bytes);
+/* f[c] = the bound objective (either ABI) at row c of x (count rows of n doubles, host memory), grad (may be NULL): count rows of n —
+ * one launch of the user's kernel with sign +1 whatever the direction of optimisation.  For checking a model and its gradient
+ * before a run. */
+nlopt_result nlopt_amd_eval_device_objective(nlopt_opt opt, size_t count, const double *x, double *f, double *grad);
 
 /* ---- user-supplied device constraints (NLOPT_GN_ISRES evaluates them on the device) --------------------------------
  * code_object / name: a gfx950 code object whose source describes a block of m constraint values with
@@ -80,6 +93,15 @@ nlopt_result nlopt_amd_add_inequality_device_mconstraint(nlopt_opt opt, unsigned
                                                          nlopt_mfunc host_twin, void *data, const double *tol);
 nlopt_result nlopt_amd_add_equality_device_mconstraint(nlopt_opt opt, unsigned m, const char *code_object, const char *name,
                                                        nlopt_mfunc host_twin, void *data, const double *tol);
+/* ... the same for a block described with NLOPT_AMD_DEVICE_CONSTRAINTS_DATA (kernel <name>_coneval_d): dev_bytes bytes at dev_data are
+ * copied at the call into device memory the block owns, as it owns its kernel, and handed to every launch.  twin_data is the host
+ * twin's.  dev_data == NULL with dev_bytes > 0, or data for an ABI-1 block: NLOPT_INVALID_ARGS, nothing added. */
+nlopt_result nlopt_amd_add_inequality_device_mconstraint_data(nlopt_opt opt, unsigned m, const char *code_object, const char *name,
+                                                              nlopt_mfunc host_twin, void *twin_data, const double *tol, const void *dev_data,
+                                                              size_t dev_bytes);
+nlopt_result nlopt_amd_add_equality_device_mconstraint_data(nlopt_opt opt, unsigned m, const char *code_object, const char *name,
+                                                            nlopt_mfunc host_twin, void *twin_data, const double *tol, const void *dev_data,
+                                                            size_t dev_bytes);
 int nlopt_amd_device_constraint_count(const nlopt_opt opt);   /* bound blocks, inequality + equality */
 
 /* per-evaluation trace (same record as the oracle's): kind 0 = initial row, 1 = reflection trial,

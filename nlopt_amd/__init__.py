@@ -192,6 +192,10 @@ def lib():
     for nm in ("nlopt_amd_add_inequality_device_mconstraint", "nlopt_amd_add_equality_device_mconstraint"):
         getattr(L, nm).argtypes = [vp, C.c_uint, C.c_char_p, C.c_char_p, vp, vp, dpp]
     L.nlopt_amd_device_constraint_count.argtypes = [vp]
+    for nm in ("nlopt_amd_add_inequality_device_mconstraint_data", "nlopt_amd_add_equality_device_mconstraint_data"):
+        getattr(L, nm).argtypes = [vp, C.c_uint, C.c_char_p, C.c_char_p, vp, vp, dpp, vp, C.c_size_t]
+    L.nlopt_amd_set_device_objective_data.argtypes = [vp, vp, C.c_size_t]
+    L.nlopt_amd_eval_device_objective.argtypes = [vp, C.c_size_t, dpp, dpp, dpp]
     if hasattr(L, "nla_k_isres_eval_cv"):       # (not in the emulated device layer: no code object loads there, so nothing needs it)
         L.nla_k_isres_eval_cv.argtypes = [C.c_int, C.c_int, C.c_int, vp, C.c_int64, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp, vp, vp, vp]
     L.nla_dev_malloc_uncached.argtypes = [C.c_size_t]
@@ -453,6 +457,15 @@ def rccl_unique_id():
     return buf.raw
 
 
+def _data_bytes(data):
+    """a data block for a device objective / constraint block as bytes (None stays None: no data)"""
+    if data is None:
+        return None
+    if isinstance(data, (bytes, bytearray, memoryview)):
+        return bytes(data)
+    return np.ascontiguousarray(data).tobytes()
+
+
 class Opt:
     """Mirror of the reference's `nlopt.opt` Python class over the C API (subset used by the hot path)."""
 
@@ -471,6 +484,16 @@ class Opt:
         h, self._h = getattr(self, "_h", None), None
         if h:
             self._L.nlopt_destroy(h)
+
+    def copy(self):
+        """nlopt_copy: an independent Opt with the same settings; a bound device objective's kernel and data block are shared
+        (reference counted), and the Python callbacks this object keeps alive stay alive with the copy"""
+        h = self._L.nlopt_copy(self._h)
+        if not h:
+            raise MemoryError("nlopt_copy failed")
+        c = Opt.__new__(Opt)
+        c._L, c._h, c.n, c._keep, c._trace, c._last, c._minf = self._L, h, self.n, list(self._keep), None, None, None
+        return c
 
     def _ck(self, ret):
         if ret < 0:
@@ -499,6 +522,26 @@ class Opt:
         fn = self._L.nlopt_amd_set_max_device_objective if maximize else self._L.nlopt_amd_set_min_device_objective
         fn.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_void_p, C.c_void_p]
         return fn(self._h, code_object.encode(), name.encode(), self._fptr(host_twin) if host_twin is not None else None, None)
+
+    def set_device_objective_data(self, data):
+        """the data the bound ABI-2 device objective reads (NLOPT_AMD_DEVICE_OBJECTIVE_DATA / _RESIDUALS of nlopt_amd_device.h): a numpy
+        array or bytes, copied to the device at the call; None or empty clears it.  Belongs to this Opt: a copy shares it until either
+        side sets data again."""
+        buf = _data_bytes(data)
+        return self._L.nlopt_amd_set_device_objective_data(self._h, buf, len(buf) if buf is not None else 0)
+
+    def eval_device_objective(self, X, grad=False):
+        """f (and, grad=True, the gradient) of the bound device objective at the rows of X, one launch of the user's kernel: f of shape
+        (count,), or (f, G) with G of shape (count, n).  A single point (shape (n,)) gives a float, or (float, g)."""
+        X = np.ascontiguousarray(X, dtype=np.float64)
+        single = X.ndim == 1
+        X = X.reshape(-1, self.n)
+        f = np.empty(X.shape[0])
+        G = np.empty_like(X) if grad else None
+        self._ck(self._L.nlopt_amd_eval_device_objective(self._h, X.shape[0], _dp(X), _dp(f), _dp(G) if grad else None))
+        if single:
+            return (float(f[0]), G[0]) if grad else float(f[0])
+        return (f, G) if grad else f
 
     def set_lower_bounds(self, lb):
         if np.isscalar(lb):
@@ -538,8 +581,10 @@ class Opt:
             data[2 * q], data[2 * q + 1] = q, count
             self._ck(add(self._h, cb, C.addressof(data) + 8 * q, float(tol)))
 
-    def _add_device_constraints(self, equality, code_object, name, m, host_twin, tol):
+    def _add_device_constraints(self, equality, code_object, name, m, host_twin, tol, data=None):
         fn = self._L.nlopt_amd_add_equality_device_mconstraint if equality else self._L.nlopt_amd_add_inequality_device_mconstraint
+        if data is not None:
+            fn = self._L.nlopt_amd_add_equality_device_mconstraint_data if equality else self._L.nlopt_amd_add_inequality_device_mconstraint_data
         twin = None
         if host_twin is not None:
             def _cb(mm, res, n, x, g, d):
@@ -552,17 +597,23 @@ class Opt:
         t = None
         if tol is not None:
             t = np.ascontiguousarray(np.broadcast_to(np.asarray(tol, dtype=np.float64), (int(m),)))
-        return fn(self._h, int(m), code_object.encode() if code_object is not None else None, name.encode() if name is not None else None,
-                  twin, None, _dp(t) if t is not None else None)
+        args = (self._h, int(m), code_object.encode() if code_object is not None else None, name.encode() if name is not None else None,
+                twin, None, _dp(t) if t is not None else None)
+        if data is not None:
+            buf = _data_bytes(data)
+            return fn(*args, buf, len(buf))
+        return fn(*args)
 
-    def add_inequality_device_constraints(self, code_object, name, m, host_twin=None, tol=None):
+    def add_inequality_device_constraints(self, code_object, name, m, host_twin=None, tol=None, data=None):
         """bind a block of m user-supplied device constraints g_j(x) <= 0 (include/nlopt_amd_device.h): kernel <name>_coneval of the
-        code object; host_twin(x) -> sequence of m values is what the host paths call; tol: scalar or m tolerances (None: zeros)"""
-        return self._add_device_constraints(False, code_object, name, m, host_twin, tol)
+        code object; host_twin(x) -> sequence of m values is what the host paths call; tol: scalar or m tolerances (None: zeros);
+        data (numpy array or bytes): what an ABI-2 block (NLOPT_AMD_DEVICE_CONSTRAINTS_DATA, kernel <name>_coneval_d) reads, copied
+        to the device at the call"""
+        return self._add_device_constraints(False, code_object, name, m, host_twin, tol, data)
 
-    def add_equality_device_constraints(self, code_object, name, m, host_twin=None, tol=None):
+    def add_equality_device_constraints(self, code_object, name, m, host_twin=None, tol=None, data=None):
         """... the same as equality constraints h_j(x) == 0"""
-        return self._add_device_constraints(True, code_object, name, m, host_twin, tol)
+        return self._add_device_constraints(True, code_object, name, m, host_twin, tol, data)
 
     def device_constraint_count(self):
         return self._L.nlopt_amd_device_constraint_count(self._h)

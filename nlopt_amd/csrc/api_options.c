@@ -47,7 +47,7 @@ void nlopt_destroy(nlopt_opt opt)
 {
     unsigned i;
     if (!opt) return;
-    if (opt->munge_on_destroy) opt->munge_on_destroy(opt->f_data);
+    if (opt->munge_on_destroy && !(opt->userobj && opt->f_data == (void *) opt->userobj)) opt->munge_on_destroy(opt->f_data);   /* (never the library's own block, userobj.c) */
     free_constraints(opt, &opt->fc, &opt->m, &opt->m_alloc, 1);
     free_constraints(opt, &opt->h, &opt->p, &opt->p_alloc, 1);
     for (i = 0; i < opt->nparams; ++i) free(opt->params[i].name);
@@ -112,8 +112,13 @@ nlopt_opt nlopt_copy(const nlopt_opt opt)
     c->params = NULL; c->nparams = 0;
     c->local_opt = NULL; c->errmsg = NULL; c->force_stop_child = NULL;
     c->trace = NULL; c->trace_cap = c->trace_len = 0;
-    nla_userobj_retain(c->userobj);              /* shared, reference counted */
-    if (c->munge_on_copy && c->f_data && !(c->f_data = c->munge_on_copy(c->f_data))) goto oom;
+    if (opt->userobj) {
+        /* a user device objective: the copy gets its own share of the kernel and of the data block (userobj.c), and its callback's data
+         * is that share — the library's, so never shown to the caller's hook */
+        if (!(c->userobj = nla_userobj_clone(opt->userobj))) { c->f_data = NULL; goto oom; }
+        if (opt->f_data == opt->userobj) c->f_data = c->userobj;
+        else if (c->munge_on_copy && c->f_data && !(c->f_data = c->munge_on_copy(c->f_data))) goto oom;
+    } else if (c->munge_on_copy && c->f_data && !(c->f_data = c->munge_on_copy(c->f_data))) goto oom;
     if (opt->n > 0) {
         if (!(c->lb = dup_doubles(opt->lb, opt->n)) || !(c->ub = dup_doubles(opt->ub, opt->n))) goto oom;
         if (opt->xtol_abs && !(c->xtol_abs = dup_doubles(opt->xtol_abs, opt->n))) goto oom;
@@ -193,7 +198,7 @@ static nlopt_result set_objective(nlopt_opt opt, nlopt_func f, nlopt_precond pre
 {
     if (!opt) return NLOPT_INVALID_ARGS;
     nla_unset_errmsg(opt);
-    if (opt->munge_on_destroy) opt->munge_on_destroy(opt->f_data);
+    if (opt->munge_on_destroy && !(opt->userobj && opt->f_data == (void *) opt->userobj)) opt->munge_on_destroy(opt->f_data);   /* (never the library's own block, userobj.c) */
     nla_userobj_release(opt->userobj);           /* a user device objective (userobj.c) goes with the objective it was bound as */
     opt->userobj = NULL;
     opt->f = f; opt->f_data = f_data; opt->pre = pre; opt->maximize = maximize;

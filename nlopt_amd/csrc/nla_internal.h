@@ -84,7 +84,7 @@ struct nlopt_opt_s {
     nlopt_amd_stats stats;
     nlopt_amd_progress_fn progress; void *progress_data;
     nlopt_amd_comm *comm;           /* multi-GPU run: borrowed communicator (comm.c), NULL = single process */
-    struct nla_userobj *userobj;    /* user-supplied device objective (userobj.c), shared by copies (reference counted) */
+    struct nla_userobj *userobj;    /* user-supplied device objective (userobj.c): this optimiser's share of the kernel (reference counted) + its data */
     int dev_sign;                   /* -1 while a maximisation runs on a device objective without the host flip wrapper */
 };
 
@@ -102,7 +102,7 @@ int nla_exact_mode(nlopt_opt opt);                    /* nlopt_set_param(opt, "a
 int nla_exact_mode_for(nlopt_opt opt, nlopt_opt also, const nla_evaluator *ev);   /* unset: exact order iff the objective is a host callback */
 
 /* user device objectives (userobj.c) */
-nla_userobj *nla_userobj_retain(nla_userobj *u);
+nla_userobj *nla_userobj_clone(const nla_userobj *u);   /* nlopt_copy: the same loaded kernel and data block, owned by the copy */
 void nla_userobj_release(nla_userobj *u);
 int nla_userobj_is_adapter(nlopt_func f);
 /* F[c] = sign * f(row c of X), G row c = sign * gradient (G may be NULL), c < count; rows ld apart */

@@ -26,12 +26,28 @@ def kernels(objdir=os.path.join(ROOT, "nlopt_amd", "lib", "obj")):
                                 "--output=" + elf], capture_output=True)
             if r.returncode:
                 continue
-            notes = subprocess.run([LLVM + "/llvm-readelf", "--notes", elf], capture_output=True, text=True).stdout
-            for blk in re.split(r"\n\s*- \.agpr_count:", notes)[1:]:
-                g = lambda k: (re.search(r"\.%s:\s*(\S+)" % k, blk) or [None, "?"])[1]
-                out.append(dict(file=f, name=g("name"), vgpr=g("vgpr_count"), agpr=blk.split()[0], sgpr=g("sgpr_count"), scratch=g("private_segment_fixed_size"),
-                                lds=g("group_segment_fixed_size"), vgpr_spill=g("vgpr_spill_count"), sgpr_spill=g("sgpr_spill_count")))
+            out += code_object_kernels(elf, f)
             os.remove(fat)
+    return out
+
+
+def code_object_kernels(elf, label=None):
+    """the same records for one plain gfx950 code object (hipcc --genco: a user's device objective, include/nlopt_amd_device.h)"""
+    out = []
+    label = label or os.path.basename(elf)
+    with tempfile.TemporaryDirectory() as td:
+        # (hipcc --genco writes an offload bundle around the ELF; the library's objects are unbundled by the caller)
+        inner = os.path.join(td, "inner.elf")
+        r = subprocess.run([LLVM + "/clang-offload-bundler", "--type=o", "--unbundle", "--input=" + elf, "--targets=hipv4-amdgcn-amd-amdhsa--gfx950",
+                            "--output=" + inner], capture_output=True)
+        if r.returncode == 0 and os.path.exists(inner) and os.path.getsize(inner) > 0:
+            elf = inner
+        notes = subprocess.run([LLVM + "/llvm-readelf", "--notes", elf], capture_output=True, text=True).stdout
+    for blk in re.split(r"\n\s*- \.agpr_count:", notes)[1:]:
+        g = lambda k: (re.search(r"\.%s:\s*(\S+)" % k, blk) or [None, "?"])[1]
+        out.append(dict(file=label, name=g("name"), vgpr=g("vgpr_count"), agpr=blk.split()[0], sgpr=g("sgpr_count"),
+                        scratch=g("private_segment_fixed_size"), lds=g("group_segment_fixed_size"), vgpr_spill=g("vgpr_spill_count"),
+                        sgpr_spill=g("sgpr_spill_count")))
     return out
 
 
