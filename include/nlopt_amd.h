@@ -77,6 +77,49 @@ nlopt_result nlopt_amd_set_device_objective_data(nlopt_opt opt, const void *data
  * one launch of the user's kernel with sign +1 whatever the direction of optimisation.  For checking a model and its gradient
  * before a run. */
 nlopt_result nlopt_amd_eval_device_objective(nlopt_opt opt, size_t count, const double *x, double *f, double *grad);
+/* Data for a bound ABI-3 objective (NLOPT_AMD_DEVICE_OBJECTIVE_ROWS / NLOPT_AMD_DEVICE_RESIDUALS_ROWS; kernel <name>_evalgrad_r): `rows`
+ * blocks of row_bytes bytes, contiguous at `data`, are copied AT THE CALL into device memory the library owns, row_stride =
+ * round_up(row_bytes, 256) bytes apart (every row 256-byte aligned).  Ownership as nlopt_amd_set_device_objective_data: immutable,
+ * reference counted, shared by nlopt_copy, released by nlopt_set_min/max_objective and nlopt_destroy; rows == 0 clears it.
+ * With such an objective bound, search i of nlopt_amd_optimize_batch reads row i (count <= rows), nlopt_amd_eval_device_objective
+ * evaluates point c on row c (count <= rows), and nlopt_optimize is refused (NLOPT_INVALID_ARGS, "a row-data objective runs through
+ * nlopt_amd_optimize_batch").  NLOPT_INVALID_ARGS with an errmsg, nothing changed: no objective bound, the bound one is ABI 1 or 2
+ * (and nlopt_amd_set_device_objective_data on an ABI-3 objective likewise), data == NULL or row_bytes == 0 with rows > 0.
+ * Out of scope: a block shared by all rows beside the per-row block. */
+nlopt_result nlopt_amd_set_device_objective_row_data(nlopt_opt opt, size_t rows, size_t row_bytes, const void *data);
+
+/* ---- batched local searches: many starts (and, with an ABI-3 objective, per-search data) in one call --------------------------------
+ * `count` independent local searches of opt's algorithm from the rows of x (count x n, host; starts in, minimisers out), run side by
+ * side in the library's batched kernels: minf[i], results[i] and numevals[i] (may be NULL) are what search i ended with.
+ *
+ * Served: NLOPT_LD_LBFGS; NLOPT_LD_MMA without nonlinear constraints — both with a compiled-in device objective, a user device
+ * objective or an ordinary host callback (called on the caller's thread, in ascending search order within a step of the batch);
+ * NLOPT_LN_COBYLA without constraints on a device objective (compiled-in or user) at a dimension the device launchers serve.  COBYLA
+ * searches always run on the device here, whatever the batch size, so a search's bits do not depend on `count`.
+ *
+ * Refused with NLOPT_INVALID_ARGS and an errmsg, opt and x untouched: any other algorithm; nonlinear constraints; any lb[i] == ub[i]
+ * (fixed coordinates are not eliminated here: out of scope); a communicator (nlopt_amd_set_comm); count == 0 or a NULL array;
+ * count > INT_MAX; a start outside the box; an ABI-3 objective with count > rows.  NLOPT_FAILURE: no device.
+ *
+ * Stopping criteria: stopval, ftol_*, xtol_*, x_weights, maxeval, vector_storage, tolg, the MMA parameters and initial_step apply to
+ * EACH search on its own (as MLSL treats its local optimiser).  maxtime and nlopt_force_stop apply to the call: unfinished searches
+ * report NLOPT_MAXTIME_REACHED / NLOPT_FORCED_STOP with their best point so far.  The call returns NLOPT_SUCCESS when every search has
+ * a result, whatever its sign; NLOPT_FORCED_STOP / NLOPT_MAXTIME_REACHED when it ended that way.  nlopt_get_numevals: the sum over the
+ * searches.  No trace is written.  Under nlopt_set_max_objective the sign is applied on the device (device objectives) and minf[i] is
+ * the true maximum.  "amd_exact_dot" as for a lone run.
+ *
+ * Contract: search i returns exactly what nlopt_optimize on the same optimiser returns from x_i alone — x and minf bit for bit, the
+ * result code, the evaluation count.  (LN_COBYLA, whose lone run is the host algorithm: what a batch of one through this entry
+ * returns.)  With an ABI-3 objective: what nlopt_optimize returns for the same model under the ABI-2 macro with data block i.
+ *
+ * Memory: at most `cap` searches run per launch, cap chosen from the free device memory and the per-search work sizes; a larger batch
+ * runs in consecutive chunks, and results do not depend on the chunking.  Parameters: "amd_batch_chunk" (0 = automatic) forces the
+ * chunk size; "amd_batch_host_list" (default 1) = 0 builds the waiting list of a user kernel's coroutine step on the device. */
+nlopt_result nlopt_amd_optimize_batch(nlopt_opt opt, size_t count, double *x, double *minf, nlopt_result *results, int *numevals);
+/* the last nlopt_amd_optimize_batch of opt with a user's kernel: coroutine steps whose waiting list was built on the device
+ * (nla_k_local_waiting_list, "amd_batch_host_list" = 0) instead of by the host loop.  0: the host loop built them (the default, or a
+ * device layer without the launcher).  A counter of its own beside nlopt_amd_stats, whose layout stays as it is. */
+uint64_t nlopt_amd_local_list_launches(const nlopt_opt opt);
 
 /* ---- user-supplied device constraints (NLOPT_GN_ISRES evaluates them on the device) --------------------------------
  * code_object / name: a gfx950 code object whose source describes a block of m constraint values with
@@ -550,6 +593,11 @@ typedef struct {
     int32_t forced, timeout;       /* the caller's nlopt_force_stop flag / maxtime verdict at this launch (stop.c:141-159) */
     int32_t pad;
 } nla_local_ext;
+/* replaces: the host loop over the request records between two launches of a coroutine batch (lbfgs_driver.c, nla_local_ctx_run) —
+ * list[0 .. *n_waiting) = in ASCENDING search index, i for a search in state 1 that wants its gradient (want_grad & 1), -(i + 1) for one
+ * that wants the value only: what nla_userobj_evalgrad_list takes.  One workgroup, no atomics: the list is the host loop's entry for
+ * entry.  list holds `count` entries; n_waiting is a device word.  (hip/local_list.hip) */
+int nla_k_local_waiting_list(const nla_local_req *req, int count, int32_t *list, int32_t *n_waiting, void *stream);
 
 /* ---- LD_LBFGS (src/algs/luksan/plis.c), batched ----------------------------------------------------- */
 /* exact != 0: every dot product / norm / objective sum accumulated in the reference's sequential order (mssubs.c:601-641,
@@ -699,7 +747,8 @@ int nla_dev_count(void);
 int nla_dev_set(int dev);
 void *nla_dev_malloc(size_t bytes);
 void nla_dev_free(void *p);
-void *nla_dev_malloc_uncached(size_t bytes);    /* MTYPE UC device memory: coherent between workgroups / XCDs without cache maintenance */
+size_t nla_dev_mem_free_bytes(void);            /* free device memory right now; 0: unknown */
+void *nla_dev_malloc_uncached(size_t bytes);   /* MTYPE UC device memory: coherent between workgroups / XCDs without cache maintenance */
 void nla_debug_uncached_stats(long out[4]);     /* [0] uncached allocations made, [1] returned to the driver (never, with the pool), [2] pooled blocks, [3] in use */
 void nla_dev_free_uncached(void *p);            /* back to the library's pool (per device; nothing returns to the driver while an uncached block of the device is in use; idle blocks above 1 GiB are trimmed when the last one is released — devrt.hip) */
 size_t nlopt_amd_release_device_memory(void);   /* gives every idle pooled block back to the driver (between the large runs of a long-lived process); bytes released */

@@ -194,16 +194,31 @@ __device__ __forceinline__ void evalgrad_wave_d(int n, const double *x, double *
     if (g) for (int i = lane; i < n; i += 64) g[i] = sign * OBJ::grad(n, i, x, A, B, data, bytes);
 }
 
+/* the block candidate `row` reads: ABI 2 (row_stride == 0, row0 == 0) the one block every candidate shares; ABI 3 the block of data
+ * row row0 + row, row_stride bytes apart */
+__device__ __forceinline__ const void *row_data(const void *data, size_t row_stride, long row0, long row)
+{
+    return (const char *) data + (size_t) (row0 + row) * row_stride;
+}
+
 template <class OBJ>
-__device__ __forceinline__ void evalgrad_kernel_body_d(int n, int ld, long count, const int *list, const double *X, double *F, double *G,
-                                                       double sign, const void *data, size_t bytes)
+__device__ __forceinline__ void evalgrad_kernel_body_rows(int n, int ld, long count, const int *list, const double *X, double *F, double *G,
+                                                          double sign, const void *data, size_t bytes, size_t row_stride, long row0)
 {
     const long c = (long) blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     if (c >= count) return;
     long row = c;
     bool wantg = G != nullptr;
     if (list) { const int e = list[c]; row = e >= 0 ? e : -(long) e - 1; wantg = wantg && e >= 0; }
-    evalgrad_wave_d<OBJ>(n, X + row * (long) ld, F + row, wantg ? G + row * (long) ld : nullptr, sign, data, bytes);
+    evalgrad_wave_d<OBJ>(n, X + row * (long) ld, F + row, wantg ? G + row * (long) ld : nullptr, sign,
+                         row_data(data, row_stride, row0, row), bytes);
+}
+
+template <class OBJ>
+__device__ __forceinline__ void evalgrad_kernel_body_d(int n, int ld, long count, const int *list, const double *X, double *F, double *G,
+                                                       double sign, const void *data, size_t bytes)
+{
+    evalgrad_kernel_body_rows<OBJ>(n, ld, count, list, X, F, G, sign, data, bytes, 0, 0);
 }
 
 template <class CON>
@@ -234,8 +249,8 @@ __device__ __forceinline__ void residual_thread_sums(int n, const double (&x)[NP
 }
 
 template <class RES, int NP>
-__device__ __forceinline__ void residuals_kernel_body(int n, int ld, long count, const int *list, const double *X, double *F, double *G,
-                                                      double sign, const void *data, size_t bytes)
+__device__ __forceinline__ void residuals_kernel_body_rows(int n, int ld, long count, const int *list, const double *X, double *F, double *G,
+                                                           double sign, const void *data_all, size_t bytes, size_t row_stride, long row0)
 {
     static_assert(NP >= 1 && NP <= 32, "NLOPT_AMD_DEVICE_RESIDUALS serves 1 <= NP <= 32");
     __shared__ double part[4][NP + 1];
@@ -245,6 +260,7 @@ __device__ __forceinline__ void residuals_kernel_body(int n, int ld, long count,
     bool wantg = G != nullptr;
     if (list) { const int e = list[c]; row = e >= 0 ? e : -(long) e - 1; wantg = wantg && e >= 0; }
     const double *xr = X + row * (long) ld;
+    const void *data = row_data(data_all, row_stride, row0, row);
     const int t = threadIdx.x, wave = t >> 6;
     double x[NP], g[NP], f = 0;
 #pragma unroll
@@ -273,6 +289,13 @@ __device__ __forceinline__ void residuals_kernel_body(int n, int ld, long count,
     if (wantg && t < n) G[row * (long) ld + t] = sign * (2 * (((part[0][1 + t] + part[1][1 + t]) + part[2][1 + t]) + part[3][1 + t]));
 }
 
+template <class RES, int NP>
+__device__ __forceinline__ void residuals_kernel_body(int n, int ld, long count, const int *list, const double *X, double *F, double *G,
+                                                      double sign, const void *data, size_t bytes)
+{
+    residuals_kernel_body_rows<RES, NP>(n, ld, count, list, X, F, G, sign, data, bytes, 0, 0);
+}
+
 }  // namespace nlopt_amd_device
 
 #define NLOPT_AMD_DEVICE_OBJECTIVE_DATA(name, OBJ)                                                                             \
@@ -297,5 +320,44 @@ __device__ __forceinline__ void residuals_kernel_body(int n, int ld, long count,
     { nlopt_amd_device::residuals_kernel_body<RES, NP>(n, ld, count, list, X, F, G, sign, data, data_bytes); }                \
     extern "C" __global__ void name##_form(int *out) { out[0] = NLOPT_AMD_DEVICE_FORM_RESIDUALS; out[1] = NP; }               \
     extern "C" __global__ void name##_abi(int *out) { *out = NLOPT_AMD_DEVICE_ABI_DATA; }
+
+/* ==== ABI 3: each candidate reads ITS OWN row of data =======================================================================
+ * Many small problems of one shape — one curve per pixel, voxel or sensor — solved side by side by nlopt_amd_optimize_batch
+ * (include/nlopt_amd.h): search i of the batch reads data row i.  The rows come from nlopt_amd_set_device_objective_row_data: `rows`
+ * blocks of row_bytes bytes each, stored row_stride = round_up(row_bytes, 256) bytes apart, so every row keeps the 256-byte
+ * alignment ABI 2 promises its one block.
+ *
+ *   NLOPT_AMD_DEVICE_OBJECTIVE_ROWS(name, OBJ)        OBJ: the struct NLOPT_AMD_DEVICE_OBJECTIVE_DATA takes, unchanged
+ *   NLOPT_AMD_DEVICE_RESIDUALS_ROWS(name, RES, NP)    RES: the struct NLOPT_AMD_DEVICE_RESIDUALS takes, unchanged
+ *
+ * A model is written once and compiled under either macro (under different names).  Kernel <name>_evalgrad_r:
+ *   (int n, int ld, long count, const int *list, const double *X, double *F, double *G, double sign,
+ *    const void *data, size_t row_bytes, size_t row_stride, long row0)
+ * The candidate in row r of X (r after `list` is resolved, as in ABI 1) hands the struct's functions
+ *   ((const char *) data + (row0 + r) * row_stride, row_bytes).
+ * Wavefront / workgroup mapping, per-thread sums, butterfly and wave combine are those of ABI 2 — the same function bodies with a
+ * data pointer computed per row — so a search on data row k gives the bits of the ABI-2 kernel handed that block alone.  The
+ * library guarantees row0 + r < rows for every candidate it launches.  <name>_abi writes 3; <name>_form as in ABI 2.
+ * Out of scope: a block shared by all rows BESIDE the per-row block (one time axis, many signals). */
+#define NLOPT_AMD_DEVICE_ABI_ROWS 3
+
+#define NLOPT_AMD_DEVICE_OBJECTIVE_ROWS(name, OBJ)                                                                             \
+    extern "C" __global__ __launch_bounds__(256) void name##_evalgrad_r(int n, int ld, long count, const int *list,            \
+                                                                        const double *X, double *F, double *G, double sign,   \
+                                                                        const void *data, size_t row_bytes,                   \
+                                                                        size_t row_stride, long row0)                         \
+    { nlopt_amd_device::evalgrad_kernel_body_rows<OBJ>(n, ld, count, list, X, F, G, sign, data, row_bytes, row_stride, row0); } \
+    extern "C" __global__ void name##_form(int *out) { out[0] = NLOPT_AMD_DEVICE_FORM_TERMS; out[1] = 0; }                    \
+    extern "C" __global__ void name##_abi(int *out) { *out = NLOPT_AMD_DEVICE_ABI_ROWS; }
+
+#define NLOPT_AMD_DEVICE_RESIDUALS_ROWS(name, RES, NP)                                                                         \
+    extern "C" __global__ __launch_bounds__(256) void name##_evalgrad_r(int n, int ld, long count, const int *list,            \
+                                                                        const double *X, double *F, double *G, double sign,   \
+                                                                        const void *data, size_t row_bytes,                   \
+                                                                        size_t row_stride, long row0)                         \
+    { nlopt_amd_device::residuals_kernel_body_rows<RES, NP>(n, ld, count, list, X, F, G, sign, data, row_bytes, row_stride,   \
+                                                            row0); }                                                          \
+    extern "C" __global__ void name##_form(int *out) { out[0] = NLOPT_AMD_DEVICE_FORM_RESIDUALS; out[1] = NP; }               \
+    extern "C" __global__ void name##_abi(int *out) { *out = NLOPT_AMD_DEVICE_ABI_ROWS; }
 
 #endif /* NLOPT_AMD_DEVICE_H */

@@ -196,6 +196,12 @@ def lib():
         getattr(L, nm).argtypes = [vp, C.c_uint, C.c_char_p, C.c_char_p, vp, vp, dpp, vp, C.c_size_t]
     L.nlopt_amd_set_device_objective_data.argtypes = [vp, vp, C.c_size_t]
     L.nlopt_amd_eval_device_objective.argtypes = [vp, C.c_size_t, dpp, dpp, dpp]
+    L.nlopt_amd_set_device_objective_row_data.argtypes = [vp, C.c_size_t, C.c_size_t, vp]
+    L.nlopt_amd_optimize_batch.argtypes = [vp, C.c_size_t, dpp, dpp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.nlopt_amd_local_list_launches.argtypes = [vp]
+    L.nlopt_amd_local_list_launches.restype = C.c_uint64
+    if hasattr(L, "nla_k_local_waiting_list"):  # (not in the emulated device layer either: the host loop builds the list there)
+        L.nla_k_local_waiting_list.argtypes = [vp, C.c_int, vp, vp, vp]
     if hasattr(L, "nla_k_isres_eval_cv"):       # (not in the emulated device layer: no code object loads there, so nothing needs it)
         L.nla_k_isres_eval_cv.argtypes = [C.c_int, C.c_int, C.c_int, vp, C.c_int64, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp, vp, vp, vp]
     L.nla_dev_malloc_uncached.argtypes = [C.c_size_t]
@@ -530,6 +536,17 @@ class Opt:
         buf = _data_bytes(data)
         return self._L.nlopt_amd_set_device_objective_data(self._h, buf, len(buf) if buf is not None else 0)
 
+    def set_device_objective_row_data(self, rows):
+        """the data rows the bound ABI-3 device objective reads (NLOPT_AMD_DEVICE_OBJECTIVE_ROWS / _RESIDUALS_ROWS of nlopt_amd_device.h):
+        a 2-d array, one row per search of optimize_batch (search i reads row i), copied to the device at the call; None or an array
+        without rows clears it"""
+        if rows is None:
+            return self._L.nlopt_amd_set_device_objective_row_data(self._h, 0, 0, None)
+        a = np.ascontiguousarray(rows)
+        if a.ndim != 2:
+            raise ValueError("set_device_objective_row_data takes a 2-d array: one row per search")
+        return self._L.nlopt_amd_set_device_objective_row_data(self._h, a.shape[0], a.shape[1] * a.itemsize, a.ctypes.data)
+
     def eval_device_objective(self, X, grad=False):
         """f (and, grad=True, the gradient) of the bound device objective at the rows of X, one launch of the user's kernel: f of shape
         (count,), or (f, G) with G of shape (count, n).  A single point (shape (n,)) gives a float, or (float, g)."""
@@ -665,7 +682,9 @@ class Opt:
     def stats(self):
         s = Stats()
         self._L.nlopt_amd_get_stats(self._h, C.byref(s))
-        return s.asdict()
+        d = s.asdict()
+        d["local_list_launches"] = self._L.nlopt_amd_local_list_launches(self._h)     # (a counter of its own beside nlopt_amd_stats)
+        return d
 
     # -- run --
     def optimize_raw(self, x0):
@@ -675,6 +694,22 @@ class Opt:
         ret = self._L.nlopt_optimize(self._h, _dp(x), C.byref(minf))
         self._last, self._minf = ret, minf.value
         return x, minf.value, ret
+
+    def optimize_batch(self, X0):
+        """nlopt_amd_optimize_batch: one local search (LD_LBFGS, LD_MMA, LN_COBYLA) from every row of X0, side by side on the device.
+        Returns (X, minf, results, numevals): the minimisers (count, n) and per search its value, nlopt_result and evaluation count.
+        The call's own result is in last_optimize_result(); a negative one other than FORCED_STOP raises."""
+        X = np.array(X0, dtype=np.float64).reshape(-1, self.n)
+        count = X.shape[0]
+        minf = np.full(count, np.nan)
+        results = np.zeros(count, dtype=np.intc)
+        nev = np.zeros(count, dtype=np.intc)
+        ret = self._L.nlopt_amd_optimize_batch(self._h, count, _dp(X), _dp(minf), results.ctypes.data_as(C.POINTER(C.c_int)),
+                                               nev.ctypes.data_as(C.POINTER(C.c_int)))
+        self._last, self._minf = ret, None
+        if ret != FORCED_STOP:
+            self._ck(ret)
+        return X, minf, results, nev
 
     def optimize(self, x0):
         x, _, ret = self.optimize_raw(x0)

@@ -23,7 +23,7 @@ static int finite_domain(unsigned n, const double *lb, const double *ub)     /* 
     return 1;
 }
 
-typedef struct { nlopt_func f; nlopt_precond pre; void *f_data; } flip_data;
+typedef nla_flip_data flip_data;
 static double flipped_objective(unsigned n, const double *x, double *grad, void *data)   /* optimize.c:970-980 */
 {
     flip_data *d = (flip_data *) data;
@@ -313,30 +313,51 @@ static int objective_stays_on_device(const nlopt_opt opt)
     return 0;
 }
 
-nlopt_result nlopt_optimize(nlopt_opt opt, double *x, double *opt_f)
+/* a maximisation turned into the minimisation of -f for the length of a run (optimize.c:1014-1024), and back: on_device — the drivers
+ * negate f and its gradient on the device (nla_evaluator.sign) — or through the flipped host callback.  Shared by nlopt_optimize and
+ * nlopt_amd_optimize_batch (batch_driver.c); d lives in the caller's frame for the whole run. */
+void nla_direction_enter(nlopt_opt opt, int on_device, nla_run_direction *d)
 {
-    nlopt_func f; void *f_data; nlopt_precond pre;
-    flip_data fd;
-    best_seen mm;
-    int maximize, memo = 0, computed = 1;
-    nlopt_result ret;
-    nla_unset_errmsg(opt);
-    if (!opt || !opt_f || !opt->f) { if (opt) nla_set_errmsg(opt, "NULL args to nlopt_optimize"); return NLOPT_INVALID_ARGS; }
-    f = opt->f; f_data = opt->f_data; pre = opt->pre;
-    nlopt_set_force_stop(opt, 0);
-    opt->force_stop_child = NULL;
-    if ((maximize = opt->maximize)) {          /* minimise -f (optimize.c:1014-1024) */
-        if (objective_stays_on_device(opt)) {
+    d->f = opt->f; d->f_data = opt->f_data; d->pre = opt->pre;
+    if ((d->maximize = opt->maximize)) {
+        if (on_device) {
             /* a device objective stays on the device: those drivers negate f and its gradient there (nla_evaluator.sign) */
             opt->dev_sign = -1;
         } else {
-            fd.f = f; fd.f_data = f_data; fd.pre = pre;
-            opt->f = flipped_objective; opt->f_data = &fd;
+            d->fd.f = d->f; d->fd.f_data = d->f_data; d->fd.pre = d->pre;
+            opt->f = flipped_objective; opt->f_data = &d->fd;
             if (opt->pre) opt->pre = flipped_precond;
         }
         opt->stopval = -opt->stopval;
         opt->maximize = 0;
     }
+}
+void nla_direction_leave(nlopt_opt opt, const nla_run_direction *d)
+{
+    if (d->maximize) {
+        opt->maximize = d->maximize;
+        opt->dev_sign = 0;
+        opt->stopval = -opt->stopval;
+        opt->f = d->f; opt->f_data = d->f_data; opt->pre = d->pre;
+    }
+}
+
+nlopt_result nlopt_optimize(nlopt_opt opt, double *x, double *opt_f)
+{
+    nla_run_direction dir;
+    best_seen mm;
+    int maximize, memo = 0, computed = 1;
+    nlopt_result ret;
+    nla_unset_errmsg(opt);
+    if (!opt || !opt_f || !opt->f) { if (opt) nla_set_errmsg(opt, "NULL args to nlopt_optimize"); return NLOPT_INVALID_ARGS; }
+    if (nla_userobj_data_rows(opt->userobj) >= 0) {      /* (which row would a lone search read?) */
+        nla_set_errmsg(opt, "nlopt_amd: a row-data objective runs through nlopt_amd_optimize_batch");
+        return NLOPT_INVALID_ARGS;
+    }
+    nlopt_set_force_stop(opt, 0);
+    opt->force_stop_child = NULL;
+    maximize = opt->maximize;
+    nla_direction_enter(opt, maximize && objective_stays_on_device(opt), &dir);          /* minimise -f (optimize.c:1014-1024) */
     if ((memo = opt->algorithm == NLOPT_LN_COBYLA && opt->m == 0 && opt->p == 0)) {
         /* the reference returns the best FEASIBLE point any objective call of an unconstrained COBYLA run saw, not the
          * algorithm's own answer (memoize_func, optimize.c:450-508,1026-1036,1064-1071) */
@@ -354,13 +375,8 @@ nlopt_result nlopt_optimize(nlopt_opt opt, double *x, double *opt_f)
         opt->f = mm.f; opt->f_data = mm.f_data;
     }
 restore:
-    if (maximize) {
-        opt->maximize = maximize;
-        opt->dev_sign = 0;
-        opt->stopval = -opt->stopval;
-        opt->f = f; opt->f_data = f_data; opt->pre = pre;
-        if (computed) *opt_f = -*opt_f;
-    }
+    nla_direction_leave(opt, &dir);
+    if (maximize && computed) *opt_f = -*opt_f;
     return ret;
 }
 

@@ -159,7 +159,7 @@ nlopt_result nlopt_set_param(nlopt_opt opt, const char *name, double val)
         /* this library's own switches: a name it does not (or no longer) read is refused instead of being stored and silently ignored — an
          * A/B script written for a switch that has since been removed would otherwise compare two identical runs (advisor, round 5) */
         static const char *const known[] = { "amd_forward", "amd_shard", "amd_shard_windows", "amd_cu_share", "amd_max_spec", "amd_window_factor", "amd_host_eval",
-                                             "amd_exact_dot", "amd_isres_evolve_serial", "amd_isres_overlap", "amd_lbfgs_streaming", "amd_mlsl_seg_regens", "amd_cobyla_host", "amd_cobyla_min_batch", NULL };
+                                             "amd_exact_dot", "amd_isres_evolve_serial", "amd_isres_overlap", "amd_lbfgs_streaming", "amd_mlsl_seg_regens", "amd_cobyla_host", "amd_cobyla_min_batch", "amd_batch_chunk", "amd_batch_host_list", NULL };
         int k;
         for (k = 0; known[k] && strcmp(name, known[k]); ++k) { }
         if (!known[k]) return fail_msg(opt, NLOPT_INVALID_ARGS, "nlopt_amd: no such switch (the amd_* names this build reads: include/nlopt_amd.h, INTEGRATION.md E)");

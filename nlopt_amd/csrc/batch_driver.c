@@ -1,0 +1,148 @@
+/* batch_driver.c — nlopt_amd_optimize_batch (include/nlopt_amd.h): many local searches of ONE optimiser in one call.
+ *
+ * The reference has no counterpart: a caller with many starts, or with many small fits of one shape, loops over nlopt_optimize.  Here
+ * the loop is the batch dimension of the kernels that already serve MLSL's local phase — one workgroup (LD_LBFGS, LD_MMA) or one
+ * wavefront (LN_COBYLA) per search — behind the same context a lone nlopt_optimize(LD_LBFGS | LD_MMA) runs on with count = 1
+ * (lbfgs_driver.c: nla_local_batch_open / nla_local_ctx_run).  Those kernels pick their code path from the objective, n and the
+ * parameters, never from the number of searches, which is what makes search i of a batch the lone run from x_i bit for bit.
+ *
+ * What this file adds: the checks (everything is refused before anything is touched), the direction of optimisation, the chunks —
+ * at most `cap` searches per launch, cap from the free device memory — and, for a row-data objective (ABI 3, userobj.c), the first
+ * data row of each chunk. */
+#include "nla_internal.h"
+#include <limits.h>
+#include <math.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#define BATCH_FALLBACK_BUDGET ((size_t) 1 << 30)      /* a device layer that cannot say how much memory is free: chunks within 1 GiB */
+#define BATCH_MAX_CHUNK (1 << 20)
+
+nlopt_result nlopt_amd_optimize_batch(nlopt_opt opt, size_t count, double *x, double *minf, nlopt_result *results, int *numevals)
+{
+    nla_run_direction dir;
+    nla_stopping stop;
+    nla_evaluator ev;
+    nla_mma_params mma;
+    nla_lbfgs_params prm;
+    nla_lbfgs_result *res = NULL;
+    nla_local_batch B;
+    nlopt_result ret = NLOPT_FAILURE;
+    char err[200];
+    double dummy;
+    size_t first, per, budget, cap;
+    unsigned n, i;
+    int alg, mf = 0, rc, on_device, total = 0;
+    int64_t rows;
+
+    if (!opt) return NLOPT_INVALID_ARGS;
+    nla_unset_errmsg(opt);
+    memset(&mma, 0, sizeof mma);
+    memset(&B, 0, sizeof B);
+    n = opt->n;
+    if (count == 0 || !x || !minf || !results) { nla_set_errmsg(opt, "nlopt_amd_optimize_batch: count == 0 or a NULL array"); return NLOPT_INVALID_ARGS; }
+    if (count > (size_t) INT_MAX) { nla_set_errmsg(opt, "nlopt_amd_optimize_batch: count > INT_MAX"); return NLOPT_INVALID_ARGS; }
+    if (!opt->f || n == 0) { nla_set_errmsg(opt, "nlopt_amd_optimize_batch: no objective set, or n == 0"); return NLOPT_INVALID_ARGS; }
+    alg = opt->algorithm == NLOPT_LD_LBFGS ? 0 : opt->algorithm == NLOPT_LD_MMA ? 1 : opt->algorithm == NLOPT_LN_COBYLA ? 2 : -1;
+    if (alg < 0) {
+        nla_set_errmsg(opt, "nlopt_amd_optimize_batch serves NLOPT_LD_LBFGS, NLOPT_LD_MMA and NLOPT_LN_COBYLA, not %s", nlopt_algorithm_to_string(opt->algorithm));
+        return NLOPT_INVALID_ARGS;
+    }
+    if (opt->m > 0 || opt->p > 0) { nla_set_errmsg(opt, "nlopt_amd_optimize_batch: nonlinear constraints are not served"); return NLOPT_INVALID_ARGS; }
+    if (opt->comm) { nla_set_errmsg(opt, "nlopt_amd_optimize_batch: a communicator is set (nlopt_amd_set_comm): multi-rank batches are not served"); return NLOPT_INVALID_ARGS; }
+    for (i = 0; i < n; ++i)
+        if (opt->lb[i] == opt->ub[i]) {
+            nla_set_errmsg(opt, "nlopt_amd_optimize_batch: lb[%u] == ub[%u]: the elimination of fixed coordinates is out of scope here (run such a box through nlopt_optimize)", i, i);
+            return NLOPT_INVALID_ARGS;
+        }
+    for (first = 0; first < count; ++first)
+        for (i = 0; i < n; ++i) {
+            const double xi = x[first * n + i];
+            if (opt->lb[i] > opt->ub[i] || xi < opt->lb[i] || xi > opt->ub[i]) {     /* (as the prologue of a lone run checks, optimize.c:546-552) */
+                nla_set_errmsg(opt, "search %zu: bounds %u fail %g <= %g <= %g", first, i, opt->lb[i], xi, opt->ub[i]);
+                return NLOPT_INVALID_ARGS;
+            }
+        }
+    on_device = nlopt_amd_objective_id(opt->f) >= 0 || nla_userobj_is_adapter(opt->f);
+    if (alg == 2) {
+        const int user = nla_userobj_is_adapter(opt->f);
+        if (!on_device) { nla_set_errmsg(opt, "nlopt_amd_optimize_batch: LN_COBYLA is served for device objectives only (compiled-in or user-supplied)"); return NLOPT_INVALID_ARGS; }
+        if (user ? !nla_cobyla_ext_serves((int) n) : !(nla_cobyla_fits((int) n) || nla_cobyla_global_serves((int) n))) {
+            nla_set_errmsg(opt, "nlopt_amd_optimize_batch: no device LN_COBYLA launcher serves n = %u", n);
+            return NLOPT_INVALID_ARGS;
+        }
+    }
+    rows = nla_userobj_is_adapter(opt->f) ? nla_userobj_data_rows(opt->userobj) : -1;
+    if (rows >= 0 && (int64_t) count > rows) {
+        nla_set_errmsg(opt, "nlopt_amd_optimize_batch: search i reads data row i: %zu searches, %lld rows set (nlopt_amd_set_device_objective_row_data)", count, (long long) rows);
+        return NLOPT_INVALID_ARGS;
+    }
+    if (alg == 1 && (rc = nla_mma_read_params(opt, &mma))) return (nlopt_result) rc;
+    if (nla_dev_count() <= 0) { nla_set_errmsg(opt, "nlopt_amd: no HIP device visible (this library has no CPU fallback)"); return NLOPT_FAILURE; }
+
+    /* from here on the run: what nlopt_optimize does in front of a lone search */
+    nlopt_set_force_stop(opt, 0);
+    opt->force_stop_child = NULL;
+    nla_direction_enter(opt, on_device, &dir);
+    if ((ret = nla_setup_run(opt, x, &dummy, &stop)) != NLOPT_SUCCESS) goto leave;
+    ret = NLOPT_FAILURE;
+    nla_evaluator_resolve(&ev, opt, opt->f, opt->f_data);
+    memset(&prm, 0, sizeof prm);
+    prm.minf_max = stop.minf_max; prm.ftol_rel = stop.ftol_rel; prm.ftol_abs = stop.ftol_abs; prm.xtol_rel = stop.xtol_rel;
+    prm.maxeval = stop.maxeval;
+    if (alg == 0) { prm.tolg = nlopt_get_param(opt, "tolg", 0.); mf = nla_lbfgs_default_mf((int) n, (int) opt->vector_storage, stop.maxeval); }
+
+    /* the chunk: what fits half of the free memory (the other half is the caller's, and the allocator's slack) */
+    per = nla_local_ctx_bytes_per_search(alg, &ev, (int) n, mf);
+    budget = nla_dev_mem_free_bytes ? nla_dev_mem_free_bytes() / 2 : 0;
+    if (budget == 0) budget = BATCH_FALLBACK_BUDGET;
+    cap = budget / (per ? per : 1);
+    if (nlopt_get_param(opt, "amd_batch_chunk", 0.) >= 1.) cap = (size_t) nlopt_get_param(opt, "amd_batch_chunk", 0.);
+    if (cap > BATCH_MAX_CHUNK) cap = BATCH_MAX_CHUNK;
+    if (cap > count) cap = count;
+    if (cap < 1) cap = 1;
+
+    res = (nla_lbfgs_result *) malloc(sizeof *res * cap);
+    if (!res) { nla_set_errmsg(opt, "out of memory"); ret = NLOPT_OUT_OF_MEMORY; goto leave; }
+    if (nla_local_batch_open(&B, alg, &ev, (int) n, (int) cap, opt->lb, opt->ub, mf, &mma, opt->dx, &stop, nla_exact_mode_for(opt, NULL, &ev), err, sizeof err)) {
+        nla_set_errmsg(opt, "device engine: %s", err);
+        goto leave;
+    }
+    nla_local_ctx_set_stats(B.c, &opt->stats);
+    nla_local_ctx_set_cobyla_min_batch(B.c, 1);          /* never the host algorithm: a search's bits must not depend on the batch size */
+    /* the waiting list of a user kernel's step: the host loop unless "amd_batch_host_list" = 0 asks for the device-built one — measured
+     * (profiles/r11_batch_fit.txt) the device list did not win at the batch sizes tried, so the default stays where MLSL's path is */
+    opt->local_list_launches = 0;
+    nla_local_ctx_set_device_list(B.c, nlopt_get_param(opt, "amd_batch_host_list", 1.) == 0., &opt->local_list_launches);
+
+    for (first = 0; first < count; first += cap) {
+        const size_t k = count - first < cap ? count - first : cap;
+        size_t j;
+        nla_local_ctx_set_row0(B.c, (int64_t) first);
+        if (nla_local_batch_upload(&B, (int) k, x + first * n, err, sizeof err)) { nla_set_errmsg(opt, "device engine: %s", err); goto close; }
+        if ((rc = nla_local_ctx_run(B.c, (int) k, &prm, res, &stop, ev.kind == NLA_EVAL_HOST ? stop.nevals_p : NULL))) {
+            nla_set_errmsg(opt, "device engine: local-search batch failed: %s", nla_dev_error_string(rc));
+            goto close;
+        }
+        if (nla_local_batch_download(&B, (int) k, x + first * n, err, sizeof err)) { nla_set_errmsg(opt, "device engine: %s", err); goto close; }
+        for (j = 0; j < k; ++j) {
+            minf[first + j] = dir.maximize ? -res[j].f : res[j].f;
+            results[first + j] = (nlopt_result) res[j].ret;
+            if (numevals) numevals[first + j] = res[j].nevals;
+            total += res[j].nevals;
+        }
+    }
+    opt->numevals = total;                               /* (a host objective was counted call by call meanwhile: the same sum) */
+    ret = nla_stop_forced(&stop) ? NLOPT_FORCED_STOP : NLOPT_SUCCESS;
+    if (ret == NLOPT_SUCCESS && nla_stop_time(&stop))
+        for (first = 0; first < count; ++first) if (results[first] == NLOPT_MAXTIME_REACHED) { ret = NLOPT_MAXTIME_REACHED; break; }
+close:
+    nla_local_batch_close(&B);
+leave:
+    free(res);
+    nla_direction_leave(opt, &dir);
+    return ret;
+}
+
+uint64_t nlopt_amd_local_list_launches(const nlopt_opt opt) { return opt ? opt->local_list_launches : 0; }

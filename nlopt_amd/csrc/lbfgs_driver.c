@@ -62,6 +62,12 @@ struct nla_local_ctx {
     /* alg 2: batches too small to fill the device go through the host algorithm (cobyla_small_batch_on_host) */
     int cob_min_batch;
     double *h_lb, *h_ub, *h_dx, *h_xtol_abs, *h_rows;
+    /* nlopt_amd_optimize_batch (batch_driver.c): a user kernel's waiting list built on the device (nla_local_ctx_set_device_list), the first
+     * data row of this context's searches (nla_local_ctx_set_row0) */
+    int dev_list;
+    uint64_t *list_launches;       /* optional: steps whose list the device built */
+    int32_t *d_nwait, *h_nwait;    /* the list's length: device word, pinned copy */
+    int64_t row0;
 };
 
 void nla_local_ctx_destroy(nla_local_ctx *c)
@@ -70,7 +76,7 @@ void nla_local_ctx_destroy(nla_local_ctx *c)
     nla_dev_free(c->d_X); nla_dev_free(c->d_work); nla_dev_free(c->d_iwork); nla_dev_free(c->d_hist); nla_dev_free(c->d_res);
     nla_dev_free(c->d_xtol_abs); nla_dev_free(c->d_x_weights);
     nla_dev_free(c->ext.req); nla_dev_free(c->ext.EX); nla_dev_free(c->ext.EG); nla_dev_free(c->ext.EF); nla_dev_free(c->ext.save);
-    nla_dev_free(c->d_list); nla_dev_free(c->d_ftrace);
+    nla_dev_free(c->d_list); nla_dev_free(c->d_ftrace); nla_dev_free(c->d_nwait); nla_host_free(c->h_nwait);
     if (c->d_done) nla_dev_free_uncached(c->d_done);
     nla_host_free(c->h_abort); nla_host_free(c->h_req); nla_host_free(c->h_x); nla_host_free(c->h_g); nla_host_free(c->h_f);
     nla_host_free(c->h_list);
@@ -199,6 +205,37 @@ const int32_t *nla_local_ctx_finished_counter(nla_local_ctx *c, int32_t *from)
     if (!c || !c->d_done) return NULL;
     *from = c->done_expected;
     return c->d_done;
+}
+/* 1: from now on the waiting list of a user kernel's coroutine step is built by nla_k_local_waiting_list and the host reads back its
+ * length only; 0: switched off, not a user kernel's context, or a device layer without the launcher — the host loop builds it */
+int nla_local_ctx_set_device_list(nla_local_ctx *c, int on, uint64_t *launches)
+{
+    if (!c) return 0;
+    c->dev_list = 0; c->list_launches = launches;
+    if (!on || c->ev.kind != NLA_EVAL_USER || !nla_k_local_waiting_list) return 0;
+    if (!c->d_nwait) c->d_nwait = (int32_t *) nla_dev_malloc(sizeof(int32_t));
+    if (!c->h_nwait) c->h_nwait = (int32_t *) nla_host_malloc(sizeof(int32_t));
+    if (!c->d_nwait || !c->h_nwait) return 0;
+    return c->dev_list = 1;
+}
+void nla_local_ctx_set_row0(nla_local_ctx *c, int64_t row0) { if (c) c->row0 = row0; }
+
+/* device memory one search takes in a context of algorithm alg: what ctx_common and the creators above allocate per unit of cap */
+size_t nla_local_ctx_bytes_per_search(int alg, const nla_evaluator *ev, int n, int mf)
+{
+    const size_t ld = (size_t) ((n + 1) & ~1);
+    size_t b = sizeof(double) * ld + sizeof(nla_lbfgs_result);
+    if (ev->kind != NLA_EVAL_DEVICE)
+        b += sizeof(nla_local_req) + sizeof(double) * (ld + (alg == 2 ? 0 : ld) + 1) + sizeof(int32_t) +
+             (alg == 2 ? nla_cobyla_save_bytes(n) : alg == 1 ? nla_mma_save_bytes() : nla_lbfgs_save_bytes());
+    if (alg == 2)
+        b += sizeof(double) * (ev->kind == NLA_EVAL_USER ? nla_cobyla_ext_work_doubles(n, 1)
+                               : nla_cobyla_fits(n) || !nla_cobyla_global_serves(n) ? nla_cobyla_work_doubles(n, (int) ld, 1)
+                                                                                    : nla_cobyla_global_work_doubles(n, 1)) +
+             sizeof(int) * nla_cobyla_work_ints(n, 1);
+    else if (alg == 1) b += sizeof(double) * nla_mma_work_doubles((int) ld, 1);
+    else b += sizeof(double) * (nla_lbfgs_work_doubles((int) ld, mf, 1) + nla_lbfgs_hist_doubles((int) ld, mf, 1)) + sizeof(int) * ld;
+    return b;
 }
 int nla_local_ctx_alg(const nla_local_ctx *c) { return c->alg; }
 double *nla_local_ctx_X(nla_local_ctx *c) { return c->d_X; }
@@ -359,6 +396,18 @@ int nla_local_ctx_run(nla_local_ctx *c, int count, const nla_lbfgs_params *prm, 
             E.forced = stop ? nla_stop_forced(stop) : 0;
             E.timeout = stop ? nla_stop_time(stop) : 0;
             if ((rc = launch(c, count, prm, &E))) return rc;
+            if (c->dev_list) {
+                /* the list is built where the records are (hip/local_list.hip: the host loop's list entry for entry); one int32 comes back */
+                if ((rc = nla_k_local_waiting_list(E.req, count, c->d_list, c->d_nwait, c->st))) return rc;
+                if ((rc = nla_memcpy_d2h(c->h_nwait, c->d_nwait, sizeof(int32_t), c->st))) return rc;
+                if ((rc = nla_stream_sync(c->st))) return rc;
+                if (c->list_launches) ++*c->list_launches;
+                if (*c->h_nwait <= 0) break;
+                if ((rc = nla_userobj_evalgrad_list_rows(c->ev.user, c->n, c->ld, (int) *c->h_nwait, c->d_list, E.EX, E.EF, E.EG, c->ev.sign,
+                                                         c->row0, count, c->st))) return rc;
+                E.resume = 1;
+                continue;
+            }
             if ((rc = nla_memcpy_d2h(c->h_req, E.req, sizeof(nla_local_req) * (size_t) count, c->st))) return rc;
             if ((rc = nla_stream_sync(c->st))) return rc;
             for (i = 0; i < count; ++i) waiting += c->h_req[i].state == 1;
@@ -369,7 +418,7 @@ int nla_local_ctx_run(nla_local_ctx *c, int count, const nla_lbfgs_params *prm, 
                 int m = 0;
                 for (i = 0; i < count; ++i) if (c->h_req[i].state == 1) c->h_list[m++] = (c->h_req[i].want_grad & 1) ? i : -(i + 1);
                 if ((rc = nla_memcpy_h2d(c->d_list, c->h_list, sizeof(int32_t) * (size_t) m, c->st))) return rc;
-                if ((rc = nla_userobj_evalgrad_list(c->ev.user, c->n, c->ld, m, c->d_list, E.EX, E.EF, E.EG, c->ev.sign, c->st))) return rc;
+                if ((rc = nla_userobj_evalgrad_list_rows(c->ev.user, c->n, c->ld, m, c->d_list, E.EX, E.EF, E.EG, c->ev.sign, c->row0, count, c->st))) return rc;
             } else {
                 for (i = 0; i < count; ++i) {
                     const int want = c->h_req[i].want_grad;          /* bit 0: gradient wanted; bit 1: LD_MMA's uncounted call (mma.c:337-339) */
@@ -408,30 +457,74 @@ int nla_local_ctx_run(nla_local_ctx *c, int count, const nla_lbfgs_params *prm, 
     return 0;
 }
 
+/* the context a batch of local searches from host rows runs on (nla_local_run_batch below; nlopt_amd_optimize_batch, batch_driver.c):
+ * a stream, the box and the initial step on the device, the context for up to `cap` searches with the run's options set.
+ * alg 0: LD_LBFGS with mf history pairs; alg 1: LD_MMA with its parameters and optional initial step (host, n); alg 2: LN_COBYLA with
+ * its optional initial step.  0, or -1 with err filled and everything released. */
+int nla_local_batch_open(nla_local_batch *B, int alg, const nla_evaluator *ev, int n, int cap, const double *lb, const double *ub, int mf,
+                         const nla_mma_params *mma, const double *sigma_init, const nla_stopping *stop, int exact, char *err, size_t errlen)
+{
+    const int ld = (n + 1) & ~1;
+    memset(B, 0, sizeof *B);
+    B->n = n; B->ld = ld;
+    B->st = nla_stream_create();
+    if (!B->st) { snprintf(err, errlen, "stream creation failed"); return -1; }
+    B->d_lb = (double *) nla_dev_malloc(sizeof(double) * (size_t) ld);
+    B->d_ub = (double *) nla_dev_malloc(sizeof(double) * (size_t) ld);
+    if (alg != 0 && sigma_init) {
+        B->d_si = (double *) nla_dev_malloc(sizeof(double) * (size_t) ld);
+        if (!B->d_si || nla_memcpy_h2d(B->d_si, sigma_init, sizeof(double) * (size_t) n, B->st)) { snprintf(err, errlen, "upload failed"); goto fail; }
+    }
+    /* (LN_COBYLA's creator reads the box back: it goes up first) */
+    if (alg == 2 && B->d_lb && B->d_ub &&
+        (nla_memcpy_h2d(B->d_lb, lb, sizeof(double) * (size_t) n, B->st) || nla_memcpy_h2d(B->d_ub, ub, sizeof(double) * (size_t) n, B->st) ||
+         nla_stream_sync(B->st))) { snprintf(err, errlen, "upload failed"); goto fail; }
+    if (B->d_lb && B->d_ub) B->c = alg == 2 ? nla_local_ctx_create_cobyla(ev, n, cap, B->d_si, B->d_lb, B->d_ub, B->st)
+                                 : alg == 1 ? nla_local_ctx_create_mma(ev, n, cap, mma, B->d_si, B->d_lb, B->d_ub, B->st)
+                                            : nla_local_ctx_create(ev, n, cap, mf, B->d_lb, B->d_ub, B->st);
+    if (!B->c) { snprintf(err, errlen, "out of device memory"); goto fail; }
+    if (alg != 2 && (nla_memcpy_h2d(B->d_lb, lb, sizeof(double) * (size_t) n, B->st) || nla_memcpy_h2d(B->d_ub, ub, sizeof(double) * (size_t) n, B->st))) { snprintf(err, errlen, "upload failed"); goto fail; }
+    if (nla_local_ctx_set_options(B->c, exact, stop ? stop->xtol_abs : NULL, stop ? stop->x_weights : NULL)) { snprintf(err, errlen, "upload failed"); goto fail; }
+    return 0;
+fail:
+    nla_local_batch_close(B);
+    return -1;
+}
+int nla_local_batch_upload(nla_local_batch *B, int count, const double *h_X, char *err, size_t errlen)
+{
+    int i;
+    for (i = 0; i < count; ++i)
+        if (nla_memcpy_h2d(B->c->d_X + (size_t) i * B->ld, h_X + (size_t) i * B->n, sizeof(double) * (size_t) B->n, B->st)) { snprintf(err, errlen, "upload failed"); return -1; }
+    return 0;
+}
+int nla_local_batch_download(nla_local_batch *B, int count, double *h_X, char *err, size_t errlen)
+{
+    int i;
+    for (i = 0; i < count; ++i)
+        if (nla_memcpy_d2h(h_X + (size_t) i * B->n, B->c->d_X + (size_t) i * B->ld, sizeof(double) * (size_t) B->n, B->st)) { snprintf(err, errlen, "read-back failed"); return -1; }
+    if ((i = nla_stream_sync(B->st))) { snprintf(err, errlen, "read-back failed: %s", nla_dev_error_string(i)); return -1; }
+    return 0;
+}
+void nla_local_batch_close(nla_local_batch *B)
+{
+    nla_local_ctx_destroy(B->c);
+    nla_dev_free(B->d_lb); nla_dev_free(B->d_ub); nla_dev_free(B->d_si);
+    if (B->st) nla_stream_destroy(B->st);
+    memset(B, 0, sizeof *B);
+}
+
 /* `count` local searches from the rows of h_X (count x n, host), results back in h_X / res.
  * alg 0: LD_LBFGS with mf history pairs; alg 1: LD_MMA with its parameters and optional initial step (host, n) */
 int nla_local_run_batch(int alg, const nla_evaluator *ev, int n, int count, const double *lb, const double *ub, double *h_X, int mf,
                         const nla_mma_params *mma, const double *sigma_init, const nla_lbfgs_params *prm, nla_lbfgs_result *res,
                         const nla_stopping *stop, int exact, int *live_nevals, nlopt_opt trace_to, char *err, size_t errlen)
 {
-    const int ld = (n + 1) & ~1;
-    void *st = nla_stream_create();
-    double *d_lb = NULL, *d_ub = NULL, *d_si = NULL;
-    nla_local_ctx *c = NULL;
+    nla_local_batch B;
+    nla_local_ctx *c;
     int rc = -1, i;
-    if (!st) { snprintf(err, errlen, "stream creation failed"); return -1; }
-    d_lb = (double *) nla_dev_malloc(sizeof(double) * (size_t) ld);
-    d_ub = (double *) nla_dev_malloc(sizeof(double) * (size_t) ld);
-    if (alg == 1 && sigma_init) {
-        d_si = (double *) nla_dev_malloc(sizeof(double) * (size_t) ld);
-        if (!d_si || nla_memcpy_h2d(d_si, sigma_init, sizeof(double) * (size_t) n, st)) { snprintf(err, errlen, "upload failed"); goto done; }
-    }
-    if (d_lb && d_ub) c = alg == 1 ? nla_local_ctx_create_mma(ev, n, count, mma, d_si, d_lb, d_ub, st) : nla_local_ctx_create(ev, n, count, mf, d_lb, d_ub, st);
-    if (!c) { snprintf(err, errlen, "out of device memory"); goto done; }
-    if (nla_memcpy_h2d(d_lb, lb, sizeof(double) * (size_t) n, st) || nla_memcpy_h2d(d_ub, ub, sizeof(double) * (size_t) n, st)) { snprintf(err, errlen, "upload failed"); goto done; }
-    if (nla_local_ctx_set_options(c, exact, stop ? stop->xtol_abs : NULL, stop ? stop->x_weights : NULL)) { snprintf(err, errlen, "upload failed"); goto done; }
-    for (i = 0; i < count; ++i)
-        if (nla_memcpy_h2d(c->d_X + (size_t) i * ld, h_X + (size_t) i * n, sizeof(double) * (size_t) n, st)) { snprintf(err, errlen, "upload failed"); goto done; }
+    if (nla_local_batch_open(&B, alg, ev, n, count, lb, ub, mf, mma, sigma_init, stop, exact, err, errlen)) return -1;
+    c = B.c;
+    if (nla_local_batch_upload(&B, count, h_X, err, errlen)) goto done;
     if (trace_to && trace_to->trace && count == 1 && nla_local_ctx_set_ftrace(c, (int64_t) trace_to->trace_cap)) { snprintf(err, errlen, "out of device memory"); goto done; }
     if ((i = nla_local_ctx_run(c, count, prm, res, stop, live_nevals))) { snprintf(err, errlen, "local-search batch failed: %s", nla_dev_error_string(i)); goto done; }
     if (trace_to && trace_to->trace && count == 1) {
@@ -444,14 +537,10 @@ int nla_local_run_batch(int alg, const nla_evaluator *ev, int n, int count, cons
         trace_to->trace_len = (size_t) calls;
         free(tmp);
     }
-    for (i = 0; i < count; ++i)
-        if (nla_memcpy_d2h(h_X + (size_t) i * n, c->d_X + (size_t) i * ld, sizeof(double) * (size_t) n, st)) { snprintf(err, errlen, "read-back failed"); goto done; }
-    if ((i = nla_stream_sync(st))) { snprintf(err, errlen, "read-back failed: %s", nla_dev_error_string(i)); goto done; }
+    if (nla_local_batch_download(&B, count, h_X, err, errlen)) goto done;
     rc = 0;
 done:
-    nla_local_ctx_destroy(c);
-    nla_dev_free(d_lb); nla_dev_free(d_ub); nla_dev_free(d_si);
-    nla_stream_destroy(st);
+    nla_local_batch_close(&B);
     return rc;
 }
 

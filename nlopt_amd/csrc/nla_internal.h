@@ -86,6 +86,7 @@ struct nlopt_opt_s {
     nlopt_amd_comm *comm;           /* multi-GPU run: borrowed communicator (comm.c), NULL = single process */
     struct nla_userobj *userobj;    /* user-supplied device objective (userobj.c): this optimiser's share of the kernel (reference counted) + its data */
     int dev_sign;                   /* -1 while a maximisation runs on a device objective without the host flip wrapper */
+    uint64_t local_list_launches;   /* nlopt_amd_optimize_batch: steps whose waiting list the device built (nlopt_amd_local_list_launches) */
 };
 
 /* ---- how an objective is evaluated ----------------------------------------------------------------------- */
@@ -110,6 +111,11 @@ int nla_userobj_eval_rows(nla_userobj *u, int n, int ld, int64_t count, const do
 /* the same for the rows named by list[0..m): entry i >= 0: row i with its gradient; entry -(i+1): row i, value only */
 int nla_userobj_evalgrad_list(nla_userobj *u, int n, int ld, int m, const int32_t *d_list, const double *X, double *F, double *G,
                               double sign, void *stream);
+/* ... for a batch whose rows are searches row0 .. row0 + span - 1 of a larger one (nlopt_amd_optimize_batch's chunks): an ABI-3 objective
+ * hands row r of X data row row0 + r, and the launch is refused unless row0 + span <= the rows that were set; ABI 1 / 2: as above */
+int nla_userobj_evalgrad_list_rows(nla_userobj *u, int n, int ld, int m, const int32_t *d_list, const double *X, double *F, double *G,
+                                   double sign, int64_t row0, int64_t span, void *stream);
+int64_t nla_userobj_data_rows(const nla_userobj *u);    /* -1: not a row-data (ABI 3) objective; else the rows set (0: none yet) */
 
 /* user device constraints (usercon.c): a constraint entry whose mf is usercon.c's adapter owns one reference to the block in f_data */
 typedef struct nla_usercon nla_usercon;
@@ -132,6 +138,13 @@ extern nlopt_algorithm nla_local_search_alg_deriv, nla_local_search_alg_nonderiv
 extern int nla_local_search_maxeval;
 
 nlopt_result nla_optimize_limited(nlopt_opt opt, double *x, double *minf, int maxeval, double maxtime);
+/* the prologue of a run (api_optimize.c): bounds check of x, stopping criteria, counters and statistics reset */
+nlopt_result nla_setup_run(nlopt_opt opt, double *x, double *minf, nla_stopping *stop);
+/* a maximisation run as the minimisation of -f, and the optimiser put back (api_optimize.c) */
+typedef struct { nlopt_func f; nlopt_precond pre; void *f_data; } nla_flip_data;
+typedef struct { nlopt_func f; void *f_data; nlopt_precond pre; int maximize; nla_flip_data fd; } nla_run_direction;
+void nla_direction_enter(nlopt_opt opt, int on_device, nla_run_direction *d);
+void nla_direction_leave(nlopt_opt opt, const nla_run_direction *d);
 
 /* ---- collectives (comm.c) ---------------------------------------------------------------------- */
 int nla_comm_allgather_dev(nlopt_amd_comm *c, const void *d_send, void *d_recv, size_t bytes, void *stream);
@@ -289,6 +302,23 @@ static inline int nla_cobyla_ext_serves(int n)
 {
     return nla_k_cobyla_batch_ext && nla_cobyla_ext_work_doubles && nla_cobyla_save_bytes && n >= 1 && n <= NLA_COBYLA_GLOBAL_MAX_N;
 }
+/* the waiting list of a coroutine step built on the device (hip/local_list.hip) and the free-memory query nlopt_amd_optimize_batch
+ * sizes its chunks from, reached the same way: without them the host loop builds the list and the chunk size is a fixed guess */
+extern __typeof(nla_k_local_waiting_list) nla_k_local_waiting_list __attribute__((weak));
+extern __typeof(nla_dev_mem_free_bytes) nla_dev_mem_free_bytes __attribute__((weak));
+/* batch_driver.c switches these on for its contexts: the device list for a user's kernel (0 on a device layer without the launcher:
+ * the host loop stays), and the first data row of the context's searches (an ABI-3 objective; nla_userobj_evalgrad_list_rows) */
+int nla_local_ctx_set_device_list(nla_local_ctx *c, int on, uint64_t *launches /* incremented per step, or NULL */);
+void nla_local_ctx_set_row0(nla_local_ctx *c, int64_t row0);
+size_t nla_local_ctx_bytes_per_search(int alg, const nla_evaluator *ev, int n, int mf);   /* device memory one search of a context takes */
+/* the context nla_local_run_batch runs on: stream, the box (and LD_MMA's / LN_COBYLA's initial step) on the device, the options of the
+ * run.  alg 0 LD_LBFGS, 1 LD_MMA, 2 LN_COBYLA; cap searches.  nla_local_batch_close frees everything it holds. */
+typedef struct { void *st; double *d_lb, *d_ub, *d_si; nla_local_ctx *c; int n, ld; } nla_local_batch;
+int nla_local_batch_open(nla_local_batch *B, int alg, const nla_evaluator *ev, int n, int cap, const double *lb, const double *ub, int mf,
+                         const nla_mma_params *mma, const double *sigma_init, const nla_stopping *stop, int exact, char *err, size_t errlen);
+int nla_local_batch_upload(nla_local_batch *B, int count, const double *h_X, char *err, size_t errlen);      /* rows of n -> ctx X */
+int nla_local_batch_download(nla_local_batch *B, int count, double *h_X, char *err, size_t errlen);          /* and back (waits) */
+void nla_local_batch_close(nla_local_batch *B);
 int nla_local_ctx_alg(const nla_local_ctx *c);
 void nla_local_ctx_destroy(nla_local_ctx *c);
 double *nla_local_ctx_X(nla_local_ctx *c);

@@ -3,7 +3,9 @@
  * The reference has no counterpart: its objective is a host callback (src/api/nlopt.h:60-62).  SURVEY.md §8b names "an
  * additive setter" as the extension a GPU implementation needs; this is it.  A bound objective is a loaded code object
  * and its <name>_evalgrad kernel (ABI 1) or <name>_evalgrad_d kernel (ABI 2: it also reads the optimiser's data block,
- * nlopt_amd_set_device_objective_data); the algorithms reach it through nla_evaluator (kind NLA_EVAL_USER).  What they hold is the
+ * nlopt_amd_set_device_objective_data) or <name>_evalgrad_r kernel (ABI 3: each candidate reads its own data ROW,
+ * nlopt_amd_set_device_objective_row_data; served by nlopt_amd_optimize_batch alone, batch_driver.c — launch() below refuses to reach
+ * past the rows that were set); the algorithms reach it through nla_evaluator (kind NLA_EVAL_USER).  What they hold is the
  * OPTIMISER's nla_userobj — its share of the loaded kernel plus its own data — so every launch below passes that optimiser's data:
  *   populations / samples   nla_userobj_eval_rows     one launch over all rows, one wavefront per row
  *   local searches          nla_userobj_evalgrad_list  one launch per step over the searches that wait (lbfgs_driver.c)
@@ -19,7 +21,7 @@
 typedef struct {
     int refs;
     void *module, *fn;
-    int abi;                               /* 1: <name>_evalgrad; 2: <name>_evalgrad_d, which also takes the data block */
+    int abi;                               /* 1: <name>_evalgrad; 2: <name>_evalgrad_d, which also takes the data block; 3: <name>_evalgrad_r, a data row per candidate */
     int form, np;                          /* ABI 2, <name>_form: 0 one wavefront per candidate; 1 residual sums, one workgroup per candidate, n <= np */
     nlopt_func twin; void *twin_data;
     /* single-point evaluation through the kernel (adapter): one scratch set per binding — and the binding is shared by nlopt_copy
@@ -31,7 +33,7 @@ typedef struct {
 } usercore;
 
 /* the caller's data in device memory: immutable once made, reference counted, shared by nlopt_copy until one side sets data anew */
-typedef struct { int refs; void *d; size_t bytes; } userdata;
+typedef struct { int refs; void *d; size_t bytes; size_t rows, row_stride; } userdata;     /* ABI 3: `rows` blocks of `bytes`, row_stride apart */
 
 /* what an nlopt_opt owns (opt->userobj, and the f_data of its adapter callback): its share of the binding and ITS data block */
 struct nla_userobj {
@@ -67,6 +69,23 @@ static userdata *data_create(const void *src, size_t bytes)
     return d;
 }
 
+/* `rows` blocks of row_bytes (contiguous at src) copied `stride` bytes apart (the padding zeroed); NULL: failed */
+static userdata *data_create_rows(const void *src, size_t rows, size_t row_bytes, size_t stride)
+{
+    userdata *d = (userdata *) calloc(1, sizeof *d);
+    void *st = d ? nla_stream_create() : NULL;
+    /* staged through one padded host image: one copy, whatever the number of rows */
+    char *img = d && st ? (char *) calloc(rows, stride) : NULL;
+    size_t r;
+    if (img) for (r = 0; r < rows; ++r) memcpy(img + r * stride, (const char *) src + r * row_bytes, row_bytes);
+    if (img && (d->d = nla_dev_malloc(rows * stride)) && !nla_memcpy_h2d(d->d, img, rows * stride, st) && !nla_stream_sync(st)) {
+        d->refs = 1; d->bytes = row_bytes; d->rows = rows; d->row_stride = stride;
+    } else if (d) { nla_dev_free(d->d); free(d); d = NULL; }
+    free(img);
+    if (st) nla_stream_destroy(st);
+    return d;
+}
+
 /* the copy's own share of u's binding and data (nlopt_copy) */
 nla_userobj *nla_userobj_clone(const nla_userobj *u)
 {
@@ -85,20 +104,26 @@ void nla_userobj_release(nla_userobj *u)
     free(u);
 }
 
-static int launch(nla_userobj *v, int n, int ld, int64_t count, const int32_t *list, const double *X, double *F, double *G, double sign, void *stream)
+static int launch(nla_userobj *v, int n, int ld, int64_t count, const int32_t *list, const double *X, double *F, double *G, double sign,
+                  int64_t row0, int64_t span, void *stream)
 {
     /* <name>_evalgrad(int n, int ld, long count, const int *list, const double *X, double *F, double *G, double sign)
-     * <name>_evalgrad_d(the same, const void *data, size_t data_bytes) */
+     * <name>_evalgrad_d(the same, const void *data, size_t data_bytes)
+     * <name>_evalgrad_r(the same, const void *data, size_t row_bytes, size_t row_stride, long row0): row r of X reads data row row0 + r;
+     *                   the rows of X a launch may name are 0 .. span - 1 (list == NULL: span = count) */
     const usercore *u = v->core;
     int32_t an = n, ald = ld;
-    int64_t acount = count;
+    int64_t acount = count, arow0 = row0;
     double asign = sign == 0. ? 1. : sign;
     const void *adata = v->data ? v->data->d : NULL;
-    size_t abytes = v->data ? v->data->bytes : 0;
-    void *params[10];
+    size_t abytes = v->data ? v->data->bytes : 0, astride = v->data ? v->data->row_stride : 0;
+    void *params[12];
     if (count <= 0) return 0;
+    /* a row-data kernel cannot check the row it is handed: no launch may reach past the rows that were set */
+    if (u->abi == 3 && (row0 < 0 || span < count || (uint64_t) row0 + (uint64_t) span > (uint64_t) (v->data ? v->data->rows : 0))) return -1;
     params[0] = &an; params[1] = &ald; params[2] = &acount; params[3] = &list; params[4] = &X; params[5] = &F; params[6] = &G; params[7] = &asign;
     params[8] = &adata; params[9] = &abytes;       /* (ABI 1 takes the first eight) */
+    params[10] = &astride; params[11] = &arow0;    /* (ABI 3) */
     if (u->abi >= 2 && u->form == 1) {
         if (n > u->np || count > 0x7fffffff) return -1;      /* the residual kernel holds x in NP registers; one workgroup per candidate */
         return nla_module_launch(u->fn, (unsigned) count, 256, params, stream);
@@ -108,12 +133,21 @@ static int launch(nla_userobj *v, int n, int ld, int64_t count, const int32_t *l
 
 int nla_userobj_eval_rows(nla_userobj *u, int n, int ld, int64_t count, const double *X, double *F, double *G, double sign, void *stream)
 {
-    return launch(u, n, ld, count, NULL, X, F, G, sign, stream);
+    return launch(u, n, ld, count, NULL, X, F, G, sign, 0, count, stream);
+}
+int nla_userobj_evalgrad_list_rows(nla_userobj *u, int n, int ld, int m, const int32_t *d_list, const double *X, double *F, double *G,
+                                   double sign, int64_t row0, int64_t span, void *stream)
+{
+    return launch(u, n, ld, m, d_list, X, F, G, sign, row0, span, stream);
+}
+int64_t nla_userobj_data_rows(const nla_userobj *u)
+{
+    return !u || u->core->abi != 3 ? -1 : u->data ? (int64_t) u->data->rows : 0;
 }
 int nla_userobj_evalgrad_list(nla_userobj *u, int n, int ld, int m, const int32_t *d_list, const double *X, double *F, double *G,
                               double sign, void *stream)
 {
-    return launch(u, n, ld, m, d_list, X, F, G, sign, stream);
+    return launch(u, n, ld, m, d_list, X, F, G, sign, 0, m, stream);
 }
 
 /* the objective as an ordinary nlopt_func: the host twin if the user gave one, else one point through the kernel — with the data of
@@ -125,6 +159,7 @@ static double adapter(unsigned n, const double *x, double *grad, void *data)
     const int ld = (int) ((n + 1) & ~1u);
     double fv = HUGE_VAL;
     if (u->twin) return u->twin(n, x, grad, u->twin_data);
+    if (u->abi == 3) return fv;                /* a row-data objective has no single block to evaluate a lone point on (nlopt_optimize refuses it) */
     pthread_mutex_lock(&u->lock);
     if ((int) n > u->cap) {
         nla_dev_free(u->d_x); nla_dev_free(u->d_g); nla_host_free(u->h_buf);
@@ -136,7 +171,7 @@ static double adapter(unsigned n, const double *x, double *grad, void *data)
     if (u->cap >= (int) n) {
         memcpy(u->h_buf, x, sizeof(double) * n);
         if (!(nla_memcpy_h2d(u->d_x, u->h_buf, sizeof(double) * n, u->st) ||
-              launch(v, (int) n, ld, 1, NULL, u->d_x, u->d_f, grad ? u->d_g : NULL, 1., u->st) ||
+              launch(v, (int) n, ld, 1, NULL, u->d_x, u->d_f, grad ? u->d_g : NULL, 1., 0, 1, u->st) ||
               nla_memcpy_d2h(u->h_buf + 2 * (size_t) ld, u->d_f, sizeof(double), u->st) ||
               (grad && nla_memcpy_d2h(u->h_buf + ld, u->d_g, sizeof(double) * n, u->st)) || nla_stream_sync(u->st))) {
             if (grad) memcpy(grad, u->h_buf + ld, sizeof(double) * n);
@@ -184,8 +219,10 @@ static nlopt_result bind(nlopt_opt opt, const char *code_object, const char *nam
     snprintf(sym, sizeof sym, "%s_evalgrad", name);
     if (!(u->fn = nla_module_function(u->module, sym))) {
         char sym_d[256];
+        char sym_r[256];
         snprintf(sym_d, sizeof sym_d, "%s_evalgrad_d", name);
-        if (!nla_module_function(u->module, sym_d)) {
+        snprintf(sym_r, sizeof sym_r, "%s_evalgrad_r", name);
+        if (!nla_module_function(u->module, sym_d) && !nla_module_function(u->module, sym_r)) {
             nla_set_errmsg(opt, "nlopt_amd: kernel %s not found in %s (NLOPT_AMD_DEVICE_OBJECTIVE(%s, ...) of nlopt_amd_device.h defines it)", sym, code_object, name);
             core_release(u); return NLOPT_INVALID_ARGS;
         }
@@ -196,11 +233,15 @@ static nlopt_result bind(nlopt_opt opt, const char *code_object, const char *nam
     /* ABI check: <name>_abi writes the header's version: 1 -> <name>_evalgrad, 2 -> <name>_evalgrad_d and <name>_form */
     snprintf(sym, sizeof sym, "%s_abi", name);
     if (read_ints(u, sym, &abi, 1)) abi = -1;
-    if (abi == 2) {
-        snprintf(sym, sizeof sym, "%s_evalgrad_d", name);
+    if (abi == 2 || abi == 3) {
+        snprintf(sym, sizeof sym, abi == 3 ? "%s_evalgrad_r" : "%s_evalgrad_d", name);
         u->fn = nla_module_function(u->module, sym);
         snprintf(sym, sizeof sym, "%s_form", name);
         if (!u->fn || read_ints(u, sym, form, 2) || form[0] < 0 || form[0] > 1 || (form[0] == 1 && (form[1] < 1 || form[1] > 32))) {
+            if (abi == 3)
+                nla_set_errmsg(opt, "nlopt_amd: %s in %s reports ABI 3 but lacks a usable %s_evalgrad_r / %s_form (the ..._OBJECTIVE_ROWS / _RESIDUALS_ROWS macros of nlopt_amd_device.h define both)",
+                               name, code_object, name, name);
+            else
             nla_set_errmsg(opt, "nlopt_amd: %s in %s reports ABI 2 but lacks a usable %s_evalgrad_d / %s_form (the ..._DATA / _RESIDUALS macros of nlopt_amd_device.h define both)",
                            name, code_object, name, name);
             core_release(u); return NLOPT_INVALID_ARGS;
@@ -242,8 +283,38 @@ nlopt_result nlopt_amd_set_device_objective_data(nlopt_opt opt, const void *data
         nla_set_errmsg(opt, "nlopt_amd: the bound device objective is ABI 1 and takes no data (NLOPT_AMD_DEVICE_OBJECTIVE_DATA / _RESIDUALS of nlopt_amd_device.h do)");
         return NLOPT_INVALID_ARGS;
     }
+    if (opt->userobj->core->abi == 3) {
+        nla_set_errmsg(opt, "nlopt_amd: the bound device objective reads a data row per search (ABI 3): nlopt_amd_set_device_objective_row_data sets its data");
+        return NLOPT_INVALID_ARGS;
+    }
     if (!data && bytes > 0) { nla_set_errmsg(opt, "nlopt_amd: device objective data is NULL with bytes > 0"); return NLOPT_INVALID_ARGS; }
     if (bytes > 0 && !(d = data_create(data, bytes))) { nla_set_errmsg(opt, "nlopt_amd: could not copy %zu bytes of objective data to the device", bytes); return NLOPT_OUT_OF_MEMORY; }
+    data_release(opt->userobj->data);
+    opt->userobj->data = d;
+    return NLOPT_SUCCESS;
+}
+
+/* the rows an ABI-3 objective reads: `rows` blocks of row_bytes copied now, 256-byte aligned each; owned like the block above */
+nlopt_result nlopt_amd_set_device_objective_row_data(nlopt_opt opt, size_t rows, size_t row_bytes, const void *data)
+{
+    userdata *d = NULL;
+    if (!opt) return NLOPT_INVALID_ARGS;
+    nla_unset_errmsg(opt);
+    if (!opt->userobj) { nla_set_errmsg(opt, "nlopt_amd: no device objective is bound (nlopt_amd_set_min/max_device_objective comes first)"); return NLOPT_INVALID_ARGS; }
+    if (opt->userobj->core->abi != 3) {
+        nla_set_errmsg(opt, "nlopt_amd: the bound device objective is ABI %d and takes no row data (NLOPT_AMD_DEVICE_OBJECTIVE_ROWS / _RESIDUALS_ROWS of nlopt_amd_device.h do)",
+                       opt->userobj->core->abi);
+        return NLOPT_INVALID_ARGS;
+    }
+    if (rows > 0 && (!data || row_bytes == 0)) { nla_set_errmsg(opt, "nlopt_amd: device objective row data is NULL or has row_bytes == 0 with rows > 0"); return NLOPT_INVALID_ARGS; }
+    if (rows > 0) {
+        const size_t stride = (row_bytes + 255) & ~(size_t) 255;
+        if (stride < row_bytes || rows > (size_t) -1 / stride / 2) { nla_set_errmsg(opt, "nlopt_amd: device objective row data too large"); return NLOPT_INVALID_ARGS; }
+        if (!(d = data_create_rows(data, rows, row_bytes, stride))) {
+            nla_set_errmsg(opt, "nlopt_amd: could not copy %zu rows of %zu bytes of objective data to the device", rows, row_bytes);
+            return NLOPT_OUT_OF_MEMORY;
+        }
+    }
     data_release(opt->userobj->data);
     opt->userobj->data = d;
     return NLOPT_SUCCESS;
@@ -263,6 +334,11 @@ nlopt_result nlopt_amd_eval_device_objective(nlopt_opt opt, size_t count, const 
     if (!(v = opt->userobj)) { nla_set_errmsg(opt, "nlopt_amd: no device objective is bound"); return NLOPT_INVALID_ARGS; }
     if (count == 0) return NLOPT_SUCCESS;
     if (!x || !f || n == 0 || count > 0x7fffffff) { nla_set_errmsg(opt, "nlopt_amd: eval_device_objective needs points, room for f, n > 0 and count < 2^31"); return NLOPT_INVALID_ARGS; }
+    if (v->core->abi == 3 && count > (v->data ? v->data->rows : 0)) {
+        nla_set_errmsg(opt, "nlopt_amd: the bound row-data objective evaluates point c on data row c: %zu points, %zu rows set (nlopt_amd_set_device_objective_row_data)",
+                       count, v->data ? v->data->rows : (size_t) 0);
+        return NLOPT_INVALID_ARGS;
+    }
     if (v->core->abi >= 2 && v->core->form == 1 && (int) n > v->core->np) {
         nla_set_errmsg(opt, "nlopt_amd: the bound residual objective serves n <= %d", v->core->np);
         return NLOPT_INVALID_ARGS;
@@ -276,7 +352,7 @@ nlopt_result nlopt_amd_eval_device_objective(nlopt_opt opt, size_t count, const 
     memset(h, 0, sizeof(double) * ld * count);
     for (c = 0; c < count; ++c) memcpy(h + c * ld, x + c * n, sizeof(double) * n);
     if (nla_memcpy_h2d(d_X, h, sizeof(double) * ld * count, st) ||
-        launch(v, (int) n, (int) ld, (int64_t) count, NULL, d_X, d_F, d_G, 1., st) ||
+        launch(v, (int) n, (int) ld, (int64_t) count, NULL, d_X, d_F, d_G, 1., 0, (int64_t) count, st) ||
         nla_memcpy_d2h(f, d_F, sizeof(double) * count, st) || nla_stream_sync(st)) { nla_set_errmsg(opt, "nlopt_amd: user objective launch failed"); goto done; }
     if (grad) {
         if (nla_memcpy_d2h(h, d_G, sizeof(double) * ld * count, st) || nla_stream_sync(st)) { nla_set_errmsg(opt, "nlopt_amd: user objective launch failed"); goto done; }
