@@ -593,7 +593,7 @@ typedef struct {
     int32_t forced, timeout;       /* the caller's nlopt_force_stop flag / maxtime verdict at this launch (stop.c:141-159) */
     int32_t pad;
 } nla_local_ext;
-/* replaces: the host loop over the request records between two launches of a coroutine batch (lbfgs_driver.c, nla_local_ctx_run) —
+/* replaces: the host loop over the request records between two launches of a coroutine batch (local_ctx.c, nla_local_ctx_run) —
  * list[0 .. *n_waiting) = in ASCENDING search index, i for a search in state 1 that wants its gradient (want_grad & 1), -(i + 1) for one
  * that wants the value only: what nla_userobj_evalgrad_list takes.  One workgroup, no atomics: the list is the host loop's entry for
  * entry.  list holds `count` entries; n_waiting is a device word.  (hip/local_list.hip) */

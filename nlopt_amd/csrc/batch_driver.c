@@ -3,7 +3,7 @@
  * The reference has no counterpart: a caller with many starts, or with many small fits of one shape, loops over nlopt_optimize.  Here
  * the loop is the batch dimension of the kernels that already serve MLSL's local phase — one workgroup (LD_LBFGS, LD_MMA) or one
  * wavefront (LN_COBYLA) per search — behind the same context a lone nlopt_optimize(LD_LBFGS | LD_MMA) runs on with count = 1
- * (lbfgs_driver.c: nla_local_batch_open / nla_local_ctx_run).  Those kernels pick their code path from the objective, n and the
+ * (local_ctx.c: nla_local_batch_open / nla_local_ctx_run).  Those kernels pick their code path from the objective, n and the
  * parameters, never from the number of searches, which is what makes search i of a batch the lone run from x_i bit for bit.
  *
  * What this file adds: the checks (everything is refused before anything is touched), the direction of optimisation, the chunks —
@@ -28,24 +28,26 @@ nlopt_result nlopt_amd_optimize_batch(nlopt_opt opt, size_t count, double *x, do
     nla_lbfgs_params prm;
     nla_lbfgs_result *res = NULL;
     nla_local_batch B;
+    nla_local_spec spec;
     nlopt_result ret = NLOPT_FAILURE;
     char err[200];
     double dummy;
     size_t first, per, budget, cap;
     unsigned n, i;
-    int alg, mf = 0, rc, on_device, total = 0;
+    int rc, on_device, total = 0;
     int64_t rows;
 
     if (!opt) return NLOPT_INVALID_ARGS;
     nla_unset_errmsg(opt);
     memset(&mma, 0, sizeof mma);
     memset(&B, 0, sizeof B);
+    memset(&spec, 0, sizeof spec);
     n = opt->n;
     if (count == 0 || !x || !minf || !results) { nla_set_errmsg(opt, "nlopt_amd_optimize_batch: count == 0 or a NULL array"); return NLOPT_INVALID_ARGS; }
     if (count > (size_t) INT_MAX) { nla_set_errmsg(opt, "nlopt_amd_optimize_batch: count > INT_MAX"); return NLOPT_INVALID_ARGS; }
     if (!opt->f || n == 0) { nla_set_errmsg(opt, "nlopt_amd_optimize_batch: no objective set, or n == 0"); return NLOPT_INVALID_ARGS; }
-    alg = opt->algorithm == NLOPT_LD_LBFGS ? 0 : opt->algorithm == NLOPT_LD_MMA ? 1 : opt->algorithm == NLOPT_LN_COBYLA ? 2 : -1;
-    if (alg < 0) {
+    spec.alg = opt->algorithm == NLOPT_LD_LBFGS ? NLA_LOCAL_LBFGS : opt->algorithm == NLOPT_LD_MMA ? NLA_LOCAL_MMA : opt->algorithm == NLOPT_LN_COBYLA ? NLA_LOCAL_COBYLA : -1;
+    if (spec.alg < 0) {
         nla_set_errmsg(opt, "nlopt_amd_optimize_batch serves NLOPT_LD_LBFGS, NLOPT_LD_MMA and NLOPT_LN_COBYLA, not %s", nlopt_algorithm_to_string(opt->algorithm));
         return NLOPT_INVALID_ARGS;
     }
@@ -65,10 +67,9 @@ nlopt_result nlopt_amd_optimize_batch(nlopt_opt opt, size_t count, double *x, do
             }
         }
     on_device = nlopt_amd_objective_id(opt->f) >= 0 || nla_userobj_is_adapter(opt->f);
-    if (alg == 2) {
-        const int user = nla_userobj_is_adapter(opt->f);
+    if (opt->algorithm == NLOPT_LN_COBYLA) {
         if (!on_device) { nla_set_errmsg(opt, "nlopt_amd_optimize_batch: LN_COBYLA is served for device objectives only (compiled-in or user-supplied)"); return NLOPT_INVALID_ARGS; }
-        if (user ? !nla_cobyla_ext_serves((int) n) : !(nla_cobyla_fits((int) n) || nla_cobyla_global_serves((int) n))) {
+        if (!nla_cobyla_device_serves(nla_userobj_is_adapter(opt->f) ? NLA_EVAL_USER : NLA_EVAL_DEVICE, (int) n)) {
             nla_set_errmsg(opt, "nlopt_amd_optimize_batch: no device LN_COBYLA launcher serves n = %u", n);
             return NLOPT_INVALID_ARGS;
         }
@@ -78,7 +79,7 @@ nlopt_result nlopt_amd_optimize_batch(nlopt_opt opt, size_t count, double *x, do
         nla_set_errmsg(opt, "nlopt_amd_optimize_batch: search i reads data row i: %zu searches, %lld rows set (nlopt_amd_set_device_objective_row_data)", count, (long long) rows);
         return NLOPT_INVALID_ARGS;
     }
-    if (alg == 1 && (rc = nla_mma_read_params(opt, &mma))) return (nlopt_result) rc;
+    if (opt->algorithm == NLOPT_LD_MMA && (rc = nla_mma_read_params(opt, &mma))) return (nlopt_result) rc;
     if (nla_dev_count() <= 0) { nla_set_errmsg(opt, "nlopt_amd: no HIP device visible (this library has no CPU fallback)"); return NLOPT_FAILURE; }
 
     /* from here on the run: what nlopt_optimize does in front of a lone search */
@@ -88,13 +89,12 @@ nlopt_result nlopt_amd_optimize_batch(nlopt_opt opt, size_t count, double *x, do
     if ((ret = nla_setup_run(opt, x, &dummy, &stop)) != NLOPT_SUCCESS) goto leave;
     ret = NLOPT_FAILURE;
     nla_evaluator_resolve(&ev, opt, opt->f, opt->f_data);
-    memset(&prm, 0, sizeof prm);
-    prm.minf_max = stop.minf_max; prm.ftol_rel = stop.ftol_rel; prm.ftol_abs = stop.ftol_abs; prm.xtol_rel = stop.xtol_rel;
-    prm.maxeval = stop.maxeval;
-    if (alg == 0) { prm.tolg = nlopt_get_param(opt, "tolg", 0.); mf = nla_lbfgs_default_mf((int) n, (int) opt->vector_storage, stop.maxeval); }
+    nla_local_params_from_stop(&prm, &stop);
+    spec.ev = &ev; spec.n = (int) n; spec.mma = &mma;
+    if (opt->algorithm == NLOPT_LD_LBFGS) { prm.tolg = nlopt_get_param(opt, "tolg", 0.); spec.mf = nla_lbfgs_default_mf((int) n, (int) opt->vector_storage, stop.maxeval); }
 
     /* the chunk: what fits half of the free memory (the other half is the caller's, and the allocator's slack) */
-    per = nla_local_ctx_bytes_per_search(alg, &ev, (int) n, mf);
+    per = nla_local_ctx_bytes_per_search(spec.alg, &ev, (int) n, spec.mf);
     budget = nla_dev_mem_free_bytes ? nla_dev_mem_free_bytes() / 2 : 0;
     if (budget == 0) budget = BATCH_FALLBACK_BUDGET;
     cap = budget / (per ? per : 1);
@@ -105,7 +105,8 @@ nlopt_result nlopt_amd_optimize_batch(nlopt_opt opt, size_t count, double *x, do
 
     res = (nla_lbfgs_result *) malloc(sizeof *res * cap);
     if (!res) { nla_set_errmsg(opt, "out of memory"); ret = NLOPT_OUT_OF_MEMORY; goto leave; }
-    if (nla_local_batch_open(&B, alg, &ev, (int) n, (int) cap, opt->lb, opt->ub, mf, &mma, opt->dx, &stop, nla_exact_mode_for(opt, NULL, &ev), err, sizeof err)) {
+    spec.cap = (int) cap;
+    if (nla_local_batch_open(&B, &spec, opt->lb, opt->ub, opt->dx, &stop, nla_exact_mode_for(opt, NULL, &ev), err, sizeof err)) {
         nla_set_errmsg(opt, "device engine: %s", err);
         goto leave;
     }

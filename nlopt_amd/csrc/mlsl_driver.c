@@ -449,7 +449,7 @@ nlopt_result nla_mlsl_minimize(nlopt_opt opt, int n, nlopt_func f, void *f_data,
     /* LN_COBYLA (GN_MLSL's default, optimize.c:763-768).  With a compiled-in device objective (round 6) the searches of a batch run
      * CONCURRENTLY on the device, one wavefront per start, like LD_LBFGS / LD_MMA: `cob_dev`.  The search's whole state is in LDS while
      * it fits a compute unit's (n <= 51, hip/cobyla_kernels.hip); beyond, up to NLA_COBYLA_GLOBAL_MAX_N, its matrices are in device
-     * memory (hip/cobyla_global.hip) — the same search, lbfgs_driver.c picks the launcher.  With a user-supplied device objective
+     * memory (hip/cobyla_global.hip) — the same search, local_ctx.c picks the launcher.  With a user-supplied device objective
      * (NLA_EVAL_USER) on one process, n <= NLA_COBYLA_GLOBAL_MAX_N, the same again as a coroutine (hip/cobyla_ext.hip): the waiting
      * searches of a batch are evaluated by ONE launch of the user's kernel per step (nla_local_ctx_run), and everything behind
      * `cob_dev` is the compiled-in case's.  Otherwise — a host callback, a user kernel on several ranks (nothing there to check it
@@ -469,8 +469,7 @@ nlopt_result nla_mlsl_minimize(nlopt_opt opt, int n, nlopt_func f, void *f_data,
     }
     nla_evaluator_resolve(&D.ev, opt, f, f_data);
     D.obj = D.ev.kind == NLA_EVAL_DEVICE ? D.ev.obj : -1;
-    cob_dev = use_cobyla && ((D.ev.kind == NLA_EVAL_DEVICE && (nla_cobyla_fits(n) || nla_cobyla_global_serves(n))) ||
-                             (D.ev.kind == NLA_EVAL_USER && nla_cobyla_ext_serves(n) && nlopt_amd_comm_world(opt ? opt->comm : NULL) == 1)) &&
+    cob_dev = use_cobyla && nla_cobyla_device_serves(D.ev.kind, n) && (D.ev.kind == NLA_EVAL_DEVICE || nlopt_amd_comm_world(opt ? opt->comm : NULL) == 1) &&
               !(opt && nlopt_get_param(opt, "amd_cobyla_host", 0) != 0) && !nlopt_get_param(local_opt, "amd_cobyla_host", 0);
     /* a fixed coordinate (lb[i] == ub[i]): the reference's nlopt_optimize_limited eliminates it in front of each COBYLA search
      * (optimize.c:412-445), the device kernel does not (it refuses such a box, include/nlopt_amd.h) — the host algorithm, whose
@@ -594,9 +593,9 @@ nlopt_result nla_mlsl_minimize(nlopt_opt opt, int n, nlopt_func f, void *f_data,
         cob_x = (double *) nla_host_malloc(sizeof(double) * (size_t) n);
         if (!cob_x) { nla_stop_msg(stop, "nlopt_amd: out of pinned memory"); ret = NLOPT_OUT_OF_MEMORY; goto done; }
     } else {
-    D.lb = cob_dev ? nla_local_ctx_create_cobyla(&D.ev, n, batch, D.d_dx, D.d_lb, D.d_ub, D.st)
-         : use_mma ? nla_local_ctx_create_mma(&D.ev, n, batch, &mma, D.d_dx, D.d_lb, D.d_ub, D.st)
-                   : nla_local_ctx_create(&D.ev, n, batch, mf, D.d_lb, D.d_ub, D.st);
+    const nla_local_spec spec = { cob_dev ? NLA_LOCAL_COBYLA : use_mma ? NLA_LOCAL_MMA : NLA_LOCAL_LBFGS, &D.ev, n, batch, mf,
+                                  use_mma ? &mma : NULL, D.d_dx, D.d_lb, D.d_ub, D.st };
+    D.lb = nla_local_ctx_create(&spec);
     if (D.lb && nla_local_ctx_set_options(D.lb, nla_exact_mode_for(opt, local_opt, &D.ev), local_opt->xtol_abs, local_opt->x_weights)) { nla_local_ctx_destroy(D.lb); D.lb = NULL; }
     /* (LD_LBFGS only: LD_MMA's launches are half as long as the distance pass beside them — behind a gate it ends after them and holds the
      * next iteration up: config 4 with LD_MMA 8.0 -> 8.3 ms per iteration, profiles/r05_mlsl_ahead_ab.txt) */

@@ -5,7 +5,7 @@
  * device kernel (hip/mma_kernels.hip): count = 1 from nlopt_optimize(LD_MMA), one workgroup per start from MLSL.
  *
  * Objectives: compiled-in device objectives (the whole search is one launch), user device objectives and ordinary host
- * callbacks (the kernel runs as a coroutine, lbfgs_driver.c).  maxtime and nlopt_force_stop are observed inside a search
+ * callbacks (the kernel runs as a coroutine, local_ctx.c).  maxtime and nlopt_force_stop are observed inside a search
  * (mma.c:258-260,394-396).  With nonlinear constraints the dual problem has variables: the outer algorithm then runs on the host
  * (mma_host.c) and solves each dual problem through this file, as the reference solves it through a nested LD_MMA. */
 #include "nla_internal.h"
@@ -33,22 +33,12 @@ int nla_mma_read_params(nlopt_opt opt, nla_mma_params *out)
 nlopt_result nla_mma_minimize(nlopt_opt opt, int n, nlopt_func f, void *f_data, const double *lb, const double *ub, double *x,
                               double *minf, nla_stopping *stop)
 {
-    nla_evaluator ev;
     nla_mma_params mma;
-    nla_lbfgs_params prm;
-    nla_lbfgs_result res;
-    char err[200];
     int rc;
     if ((rc = nla_mma_read_params(opt, &mma))) return (nlopt_result) rc;
-    if (nla_dev_count() <= 0) { nla_stop_msg(stop, "nlopt_amd: no HIP device visible (this library has no CPU fallback)"); return NLOPT_FAILURE; }
-    if (opt->m > 0) return nla_mma_constrained(opt, (unsigned) n, f, f_data, lb, ub, x, minf, stop, &mma);   /* mma_host.c */
-    nla_evaluator_resolve(&ev, opt, f, f_data);
-    memset(&prm, 0, sizeof prm);
-    prm.minf_max = stop->minf_max; prm.ftol_rel = stop->ftol_rel; prm.ftol_abs = stop->ftol_abs; prm.xtol_rel = stop->xtol_rel;
-    prm.maxeval = stop->maxeval;
-    if (nla_local_run_batch(1, &ev, n, 1, lb, ub, x, 0, &mma, opt->dx, &prm, &res, stop, nla_exact_mode_for(opt, NULL, &ev),
-                            ev.kind == NLA_EVAL_HOST ? stop->nevals_p : NULL, opt, err, sizeof err)) { nla_stop_msg(stop, "device engine: %s", err); return NLOPT_FAILURE; }
-    *minf = res.f;
-    if (ev.kind != NLA_EVAL_HOST) *stop->nevals_p += res.nevals;
-    return (nlopt_result) res.ret;
+    if (opt->m > 0) {
+        if (nla_dev_count() <= 0) { nla_stop_msg(stop, "nlopt_amd: no HIP device visible (this library has no CPU fallback)"); return NLOPT_FAILURE; }
+        return nla_mma_constrained(opt, (unsigned) n, f, f_data, lb, ub, x, minf, stop, &mma);   /* mma_host.c */
+    }
+    return nla_local_minimize_one(NLA_LOCAL_MMA, opt, n, f, f_data, lb, ub, x, minf, stop, 0, 0., &mma, opt->dx);
 }

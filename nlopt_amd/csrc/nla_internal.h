@@ -278,11 +278,23 @@ nlopt_result nla_isres_minimize(nlopt_opt opt, int n, nlopt_func f, void *f_data
 
 /* LD_LBFGS (lbfgs_driver.c) */
 int nla_lbfgs_default_mf(int n, int mf, int maxeval);
+
+/* ---- the batch context of the local optimisers (local_ctx.c) ---------------------------------------------------------------------- */
+enum { NLA_LOCAL_LBFGS = 0, NLA_LOCAL_MMA = 1, NLA_LOCAL_COBYLA = 2 };
 typedef struct nla_local_ctx nla_local_ctx;
-nla_local_ctx *nla_local_ctx_create(const nla_evaluator *ev, int n, int cap, int mf, const double *d_lb, const double *d_ub, void *stream);
-nla_local_ctx *nla_local_ctx_create_mma(const nla_evaluator *ev, int n, int cap, const nla_mma_params *alg_params, const double *d_sigma_init,
-                                        const double *d_lb, const double *d_ub, void *stream);
-nla_local_ctx *nla_local_ctx_create_cobyla(const nla_evaluator *ev, int n, int cap, const double *d_dx, const double *d_lb, const double *d_ub, void *stream);
+/* what a context is created from.  LN_COBYLA (bound constraints only) gives NULL for a host callback or a dimension no device launcher
+ * serves (nla_cobyla_device_serves below) */
+typedef struct {
+    int alg;                            /* NLA_LOCAL_* */
+    const nla_evaluator *ev;
+    int n, cap;                         /* up to cap simultaneous searches */
+    int mf;                             /* LD_LBFGS: history pairs */
+    const nla_mma_params *mma;          /* LD_MMA: the algorithm's parameters (mma_driver.c reads them) */
+    const double *d_step;               /* LD_MMA, LN_COBYLA: the initial step on the device, or NULL = the default step of every start (options.c:921-946) */
+    const double *d_lb, *d_ub;          /* the box on the device (uploaded before the call: LN_COBYLA reads it back) */
+    void *stream;
+} nla_local_spec;
+nla_local_ctx *nla_local_ctx_create(const nla_local_spec *spec);
 void nla_local_ctx_set_cobyla_min_batch(nla_local_ctx *c, int min_batch);
 /* device COBYLA beyond the LDS kernel's dimensions (hip/cobyla_global.hip).  The drivers reach its two entry points through WEAK
  * references: a device layer without them (the emulated one the CPU tests link) leaves them null, and such dimensions stay with the
@@ -302,6 +314,12 @@ static inline int nla_cobyla_ext_serves(int n)
 {
     return nla_k_cobyla_batch_ext && nla_cobyla_ext_work_doubles && nla_cobyla_save_bytes && n >= 1 && n <= NLA_COBYLA_GLOBAL_MAX_N;
 }
+/* 1: a device launcher serves LN_COBYLA for this kind of objective and n — the LDS or the global-memory kernel for a compiled-in one,
+ * the coroutine for a user's kernel, none for a host callback */
+static inline int nla_cobyla_device_serves(int kind, int n)
+{
+    return kind == NLA_EVAL_DEVICE ? nla_cobyla_fits(n) || nla_cobyla_global_serves(n) : kind == NLA_EVAL_USER && nla_cobyla_ext_serves(n);
+}
 /* the waiting list of a coroutine step built on the device (hip/local_list.hip) and the free-memory query nlopt_amd_optimize_batch
  * sizes its chunks from, reached the same way: without them the host loop builds the list and the chunk size is a fixed guess */
 extern __typeof(nla_k_local_waiting_list) nla_k_local_waiting_list __attribute__((weak));
@@ -312,14 +330,14 @@ int nla_local_ctx_set_device_list(nla_local_ctx *c, int on, uint64_t *launches /
 void nla_local_ctx_set_row0(nla_local_ctx *c, int64_t row0);
 size_t nla_local_ctx_bytes_per_search(int alg, const nla_evaluator *ev, int n, int mf);   /* device memory one search of a context takes */
 /* the context nla_local_run_batch runs on: stream, the box (and LD_MMA's / LN_COBYLA's initial step) on the device, the options of the
- * run.  alg 0 LD_LBFGS, 1 LD_MMA, 2 LN_COBYLA; cap searches.  nla_local_batch_close frees everything it holds. */
+ * run.  spec: alg, ev, n, cap, mf, mma (the stream, the box and the step on the device are set by the call from lb, ub, step: host arrays
+ * of n, step optional).  nla_local_batch_close frees everything it holds. */
 typedef struct { void *st; double *d_lb, *d_ub, *d_si; nla_local_ctx *c; int n, ld; } nla_local_batch;
-int nla_local_batch_open(nla_local_batch *B, int alg, const nla_evaluator *ev, int n, int cap, const double *lb, const double *ub, int mf,
-                         const nla_mma_params *mma, const double *sigma_init, const nla_stopping *stop, int exact, char *err, size_t errlen);
+int nla_local_batch_open(nla_local_batch *B, const nla_local_spec *spec, const double *lb, const double *ub, const double *step,
+                         const nla_stopping *stop, int exact, char *err, size_t errlen);
 int nla_local_batch_upload(nla_local_batch *B, int count, const double *h_X, char *err, size_t errlen);      /* rows of n -> ctx X */
 int nla_local_batch_download(nla_local_batch *B, int count, double *h_X, char *err, size_t errlen);          /* and back (waits) */
 void nla_local_batch_close(nla_local_batch *B);
-int nla_local_ctx_alg(const nla_local_ctx *c);
 void nla_local_ctx_destroy(nla_local_ctx *c);
 double *nla_local_ctx_X(nla_local_ctx *c);
 void nla_local_ctx_set_stats(nla_local_ctx *c, nlopt_amd_stats *stats);
@@ -329,11 +347,14 @@ const int32_t *nla_local_ctx_finished_counter(nla_local_ctx *c, int32_t *from);
 int nla_local_ctx_set_options(nla_local_ctx *c, int exact, const double *xtol_abs, const double *x_weights);
 int nla_local_ctx_run(nla_local_ctx *c, int count, const nla_lbfgs_params *prm, nla_lbfgs_result *h_res, const nla_stopping *stop,
                       int *live_nevals);
-int nla_local_run_batch(int alg, const nla_evaluator *ev, int n, int count, const double *lb, const double *ub, double *h_X, int mf,
-                        const nla_mma_params *mma, const double *sigma_init, const nla_lbfgs_params *prm, nla_lbfgs_result *res,
-                        const nla_stopping *stop, int exact, int *live_nevals, nlopt_opt trace_to, char *err, size_t errlen);
+int nla_local_run_batch(const nla_local_spec *spec, const double *lb, const double *ub, const double *step, double *h_X,
+                        const nla_lbfgs_params *prm, nla_lbfgs_result *res, const nla_stopping *stop, int exact, int *live_nevals,
+                        nlopt_opt trace_to, char *err, size_t errlen);
 int nla_local_ctx_set_ftrace(nla_local_ctx *c, int64_t cap);
 int nla_local_ctx_read_ftrace(nla_local_ctx *c, int inst, int64_t count, double *h_out);
+void nla_local_params_from_stop(nla_lbfgs_params *prm, const nla_stopping *stop);     /* the run's stopping values; tolg = 0 */
+nlopt_result nla_local_minimize_one(int alg, nlopt_opt opt, int n, nlopt_func f, void *f_data, const double *lb, const double *ub, double *x,
+                                    double *minf, nla_stopping *stop, int mf, double tolg, const nla_mma_params *mma, const double *step);
 /* LD_MMA without nonlinear constraints (mma_driver.c) */
 int nla_mma_read_params(nlopt_opt opt, nla_mma_params *out);     /* optimize.c:798-815; 0 or an nlopt_result < 0 with errmsg set */
 /* NLOPT_LN_COBYLA on the host (cobyla_host.c; reference entry cobyla_minimize, cobyla.c:181-271) */

@@ -8,7 +8,7 @@
  * past the rows that were set); the algorithms reach it through nla_evaluator (kind NLA_EVAL_USER).  What they hold is the
  * OPTIMISER's nla_userobj — its share of the loaded kernel plus its own data — so every launch below passes that optimiser's data:
  *   populations / samples   nla_userobj_eval_rows     one launch over all rows, one wavefront per row
- *   local searches          nla_userobj_evalgrad_list  one launch per step over the searches that wait (lbfgs_driver.c)
+ *   local searches          nla_userobj_evalgrad_list  one launch per step over the searches that wait (local_ctx.c)
  *   anything else           the adapter callback below: a single point through the same kernel (exact, slow) */
 #include "nla_internal.h"
 #include <math.h>

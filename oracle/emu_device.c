@@ -1,5 +1,5 @@
 /* emu_device.c — TEST INFRASTRUCTURE: a CPU stand-in for the product's *device layer*, so that the product's host drivers
- * (isres_driver.c, mlsl_driver.c, lbfgs_driver.c, mma_driver.c, mtstream.c, comm.c, the API shell) can be run without a GPU —
+ * (isres_driver.c, mlsl_driver.c, local_ctx.c, lbfgs_driver.c, mma_driver.c, mtstream.c, comm.c, the API shell) can be run without a GPU —
  * in particular by the world_size-2 gloo tests of the sharded ISRES / MLSL paths (tests/test_multiproc.py).
  *
  * It implements the C-ABI of include/nlopt_amd.h that hip/devrt.hip and the kernel launchers export: "device" memory is host

@@ -298,7 +298,7 @@ def test_cobyla_fits_the_rows_through_batches_of_one_and_all_at_once(co):
 
 # ---- the device list --------------------------------------------------------------------------------------------------------------------
 def host_list(state, want):
-    """the loop of nla_local_ctx_run (lbfgs_driver.c)"""
+    """the loop of nla_local_ctx_run (local_ctx.c)"""
     return [i if (want[i] & 1) else -(i + 1) for i in range(len(state)) if state[i] == 1]
 
 

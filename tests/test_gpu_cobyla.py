@@ -195,7 +195,7 @@ def test_gn_mlsl_batched_device_cobyla_exact_order_is_the_references_run(alg, ob
 @pytest.mark.parametrize("alg,obj,n,maxeval,pop", [(T.GN_MLSL_LDS, "rosenbrock", 4, 30000, 400), (T.GN_MLSL, "sphere", 12, 40000, 300)])
 def test_gn_mlsl_cobyla_batches_go_where_they_run_faster_and_the_run_stays_the_references(alg, obj, n, maxeval, pop):
     """the routing: a batch of fewer searches than the device needs to beat a host core runs through the host algorithm, a large one as
-    one launch (lbfgs_driver.c cob_min_batch: 24 / 12 / 6 searches by dimension; 3 here, so that the first iteration's single search
+    one launch (local_ctx.c cob_min_batch: 24 / 12 / 6 searches by dimension; 3 here, so that the first iteration's single search
     goes one way and the second iteration's batch the other).  In exact-order mode both produce the reference's searches bit for bit,
     so the whole run is the reference's whichever way each batch went"""
     r = run_gn_mlsl(T.more_bind(O.ref()), alg, obj, n, maxeval, population=pop)
