@@ -47,7 +47,45 @@
 
 static double gam(int n) { double z = n / 2; return sqrt(pow(K2PI * z, 1.0 / n) * z) * exp(-0.5); }   /* mlsl.c:227-237 */
 
+/* the objective as MLSL's local optimiser sees it (fcount, mlsl.c:246-251): every call counted where the caller can see it */
+typedef struct { nlopt_func f; void *f_data; double sign; int *nevals_p; } mlsl_count_wrap;
+
+/* who runs the local searches of a run — decided once, by mlsl_choose_local */
+typedef enum {
+    MLSL_HOST_SEARCH,               /* LN_COBYLA as a host algorithm (cobyla_host.c), one search at a time on the caller's thread */
+    MLSL_DEV_COBYLA,                /* LN_COBYLA batched on the device */
+    MLSL_LBFGS, MLSL_MMA            /* the batched device kernels (with a host callback: one search at a time, f on the caller's thread) */
+} mlsl_local;
+
+/* the state of one run: what every phase below reads, and everything the run allocates (mfree) */
 typedef struct {
+    /* the caller's */
+    nlopt_opt opt, local_opt;
+    nlopt_func f; void *f_data;     /* host evaluations (a maximisation left unflipped by the dispatcher: the flipped one, mlsl_signed_f) */
+    nla_stopping *stop;
+    /* several ranks: the clock and the force_stop flag are decided by all ranks together at the start of every phase (comm.c);
+     * sp is what those two tests look at until the next agreement (mlsl_agree) */
+    const nla_stopping *sp; nla_stopping agreed_view; int agreed_force;
+    nla_stopping lstop;             /* what a local search observes of the caller's stopping state */
+    nla_lbfgs_params prm; int loc_maxeval;
+    nla_mma_params mma;
+    mlsl_local local;
+    int host;                       /* f is called on the caller's thread: a host callback, or the host search */
+    int batch, bmax;                /* searches in flight per rank / over all ranks */
+    double R_prefactor;
+    nlopt_result ret;
+    int search_failed;              /* a local search returned an error: the result is the best point known BEFORE the iteration (the reference's goto done) */
+    double best_f; size_t best_row; int best_is_lm;
+    /* the host search: the local optimiser's own objective while this run has its wrapper installed in it, and the wrappers' data */
+    int lo_installed; nlopt_func lo_f; void *lo_fdata;
+    mlsl_count_wrap cw, sw;
+    /* per-batch arrays */
+    nla_lbfgs_result *res, *res_mine;   /* all candidates' results by gathered row (bmax) / this rank's (BATCH_MAX) */
+    size_t *cand;                   /* bmax: positions in `ord` of the batch's candidates */
+    double *Fnew;                   /* pinned, N: the samples' values come back every iteration */
+    double *cob_x;                  /* pinned, n: the host search's point */
+    int prefetch_due, ahead_due;    /* to go out in front of the next launch of local searches (mlsl_prefetch_now) */
+
     int n, ld, obj, N;
     nla_evaluator ev;
     double *h_rows;                 /* host objective: the iteration's samples, pinned (N x ld) */
@@ -114,10 +152,13 @@ typedef struct {
 #define NLA_MLSL_GATE_PCT 50        /* the sampling phase enqueued ahead starts when this share of the batch's searches have ended (0: at once) */
 #endif
 #define MFAIL(d, ...) do { snprintf((d)->err, sizeof (d)->err, __VA_ARGS__); return -1; } while (0)
-#define MCK(d, call) do { int rc_ = (call); if (rc_) MFAIL(d, "%s failed: %s", #call, nla_dev_error_string(rc_)); } while (0)
 
+/* the one teardown: everything the run allocated, and the local optimiser's own objective put back (the host search's wrapper and
+ * its data live in the caller's frame) */
 static void mfree(mlsl_dev *d)
 {
+    if (d->lo_installed) { d->local_opt->f = d->lo_f; d->local_opt->f_data = d->lo_fdata; d->lo_installed = 0; }
+    nla_host_free(d->cob_x);
     if (d->st) nla_stream_sync(d->st);
     if (d->rs) nla_stream_sync(d->rs);
     if (d->mts) { nla_mtstream_finish(d->mts, d->words_used); nla_mtstream_destroy(d->mts); }
@@ -136,6 +177,7 @@ static void mfree(mlsl_dev *d)
     nla_dev_free(d->d_D2); nla_dev_free(d->d_cpd2); nla_dev_free(d->d_cld2);
     if (d->rs && d->rs != d->st) nla_stream_destroy(d->rs);
     if (d->st) nla_stream_destroy(d->st);
+    nla_host_free(d->Fnew); free(d->res); free(d->res_mine); free(d->cand);
 }
 
 /* host arrays that travel to / from the device every iteration live in PINNED memory: a copy from pageable memory is staged by the
@@ -229,20 +271,68 @@ static int grow_lms(mlsl_dev *d, size_t need)
 /* The distance scratch grows with the point set — N x npts doubles per sampling phase, npts larger by N every iteration — and it used
  * to be reallocated to the exact size EVERY iteration: a hipFree (which waits for every stream of the device: the generator's, when it
  * works ahead on a stream of its own — why round 4's sample prefetch never overlapped anything, profiles/r04_mlsl_prefetch_timeline.txt) and
- * a hipMalloc of tens of MB between the sampling kernel and the distance pass.  Now it doubles: a handful of reallocations per run. */
-static int need_D(mlsl_dev *d, size_t doubles)
+ * a hipMalloc of tens of MB between the sampling kernel and the distance pass.  Now it doubles: a handful of reallocations per run.
+ * One rule for both scratch matrices (d_D, and d_D2 of the sampling phase enqueued ahead). */
+static int grow_scratch(mlsl_dev *d, double **buf, size_t *cap, size_t doubles, const char *what)
 {
-    if (doubles <= d->dcap) return 0;
-    if (doubles < 2 * d->dcap) doubles = 2 * d->dcap;
-    if (!d->dcap) {            /* the first allocation: the pass of the 8th iteration (N x 8 N doubles, within 1 GiB) */
+    if (doubles <= *cap) return 0;
+    if (doubles < 2 * *cap) doubles = 2 * *cap;
+    if (!*cap) {               /* the first allocation: the pass of the 8th iteration (N x 8 N doubles, within 1 GiB) */
         const size_t want = 8 * (size_t) d->N * (size_t) d->N, budget = ((size_t) 1 << 30) / sizeof(double);
         if (doubles < (want < budget ? want : budget)) doubles = want < budget ? want : budget;
     }
-    nla_dev_free(d->d_D);
-    d->d_D = (double *) nla_dev_malloc(sizeof(double) * doubles);
-    d->dcap = d->d_D ? doubles : 0;
-    if (!d->d_D) MFAIL(d, "out of device memory (distance matrix)");
+    nla_dev_free(*buf);
+    *buf = (double *) nla_dev_malloc(sizeof(double) * doubles);
+    *cap = *buf ? doubles : 0;
+    if (!*buf) MFAIL(d, "out of device memory (%s)", what);
     return 0;
+}
+static int need_D(mlsl_dev *d, size_t doubles) { return grow_scratch(d, &d->d_D, &d->dcap, doubles, "distance matrix"); }
+
+/* ---- the device passes of a sampling phase: one copy each, for the iteration's own phase (stream st, scratch d_D) and for the one
+ * enqueued ahead (stream rs, scratch d_D2).  r0, mine: the block of the N new rows this rank computes — all of them on one rank ---- */
+
+/* f of `cnt` rows on the device: compiled-in objective, or the user's kernel (host objectives are called by the host walks) */
+static int mlsl_eval_rows(mlsl_dev *d, const double *rows, int cnt, double *dF, void *stream)
+{
+    if (d->ev.kind == NLA_EVAL_USER) return nla_userobj_eval_rows(d->ev.user, d->n, d->ld, cnt, rows, dF, NULL, d->ev.sign, stream);
+    return nla_k_eval(d->obj, d->n, d->ld, rows, cnt, dF, stream) || (d->ev.sign < 0 && nla_k_mlsl_negate(dF, cnt, stream));
+}
+
+/* the N sample rows first .. first + N - 1 and, with `evaluate`, their f (mlsl.c:355-360): Sobol points by index, or the stream's words
+ * (nlopt_urand) — that kernel evaluates a compiled-in objective itself, and a device objective is evaluated on this path whether or
+ * not the host walk replaces the values afterwards (the host search on a device objective), as it always was */
+static int mlsl_sample_rows(mlsl_dev *d, void *stream, size_t first, int evaluate)
+{
+    double *rows = d->d_P + first * (size_t) d->ld, *F = d->d_F + first;
+    if (d->d_V)                                                                /* nlopt_sobol_next, mlsl.c:355 */
+        return nla_k_mlsl_sobol_rows(d->n, d->ld, d->d_lb, d->d_ub, d->d_V, d->sobol_next, d->N, rows, stream) ||
+               (evaluate && mlsl_eval_rows(d, rows, d->N, F, stream));
+    if (nla_k_crs_init_rows(d->obj, d->n, d->ld, d->d_lb, d->d_ub, d->d_words, (int64_t) first, d->N, d->d_P, d->d_F, stream)) return -1;
+    if (d->ev.kind == NLA_EVAL_DEVICE) return d->ev.sign < 0 && nla_k_mlsl_negate(F, d->N, stream);
+    return d->ev.kind == NLA_EVAL_USER && mlsl_eval_rows(d, rows, d->N, F, stream);
+}
+
+/* closest_pt_d of the new points old .. old + N - 1: over every point with smaller f; of the old, not yet minimised points: over the new
+ * points with smaller f (find_closest_pt, pts_update_newpt: mlsl.c:155-178).  Several ranks: the ROWS of the new points are dealt in
+ * blocks over the ranks; every rank computes its rows' minima and its rows' share of the column minima, combined by an element-wise
+ * min over an all-gather (exact).  cpd: the nb = old + N minima on the device; minimized: the flags, or NULL = none is */
+static int mlsl_closest_pt_pass(mlsl_dev *d, void *stream, size_t old, int r0, int mine, double *D, double *cpd, const int32_t *minimized)
+{
+    const int nb = (int) (old + (size_t) d->N);
+    const double *A = d->d_P + (old + (size_t) r0) * (size_t) d->ld, *FA = d->d_F + old + r0;
+    return mine > 0 && (nla_k_mlsl_dist2(d->n, d->ld, A, mine, d->d_P, nb, D, stream) ||
+                        nla_k_mlsl_rowmin(D, nb, mine, nb, FA, d->d_F, NULL, cpd + old + r0, stream) ||
+                        nla_k_mlsl_colmin(D, nb, mine, (int) old, FA, d->d_F, minimized, cpd, stream));
+}
+
+/* closest_lm_d of the same rows over the minima l0 .. l0 + lc - 1 (find_closest_lm, mlsl.c:139-153), into h_out[0 .. mine) */
+static int mlsl_closest_lm_pass(mlsl_dev *d, void *stream, size_t old, int r0, int mine, size_t l0, size_t lc, double *D, double *d_out, double *h_out)
+{
+    const double *A = d->d_P + (old + (size_t) r0) * (size_t) d->ld, *FA = d->d_F + old + r0;
+    return mine > 0 && lc && (nla_k_mlsl_dist2(d->n, d->ld, A, mine, d->d_LM + l0 * (size_t) d->ld, (int) lc, D, stream) ||
+                              nla_k_mlsl_rowmin(D, (int) lc, mine, (int) lc, FA, d->d_LF + l0, NULL, d_out, stream) ||
+                              nla_memcpy_d2h(h_out, d_out, sizeof(double) * (size_t) mine, stream));
 }
 
 /* ---- the next iteration's sampling phase, ahead (see mlsl_dev) ---- */
@@ -262,18 +352,7 @@ static int ahead_buffers(mlsl_dev *d, size_t doubles)
     if (!d->h_cld2) d->h_cld2 = (double *) nla_host_malloc(sizeof(double) * (size_t) d->N);
     if (!d->d_cld2) d->d_cld2 = (double *) nla_dev_malloc(sizeof(double) * (size_t) d->N);
     if (!d->Fnew2 || !d->h_cld2 || !d->d_cld2) MFAIL(d, "out of memory (sampling ahead)");
-    if (doubles > d->dcap2) {
-        if (doubles < 2 * d->dcap2) doubles = 2 * d->dcap2;
-        if (!d->dcap2) {       /* as need_D: the pass of the 8th iteration from the start, within 1 GiB */
-            const size_t want = 8 * (size_t) d->N * (size_t) d->N, budget = ((size_t) 1 << 30) / sizeof(double);
-            if (doubles < (want < budget ? want : budget)) doubles = want < budget ? want : budget;
-        }
-        nla_dev_free(d->d_D2);
-        d->d_D2 = (double *) nla_dev_malloc(sizeof(double) * doubles);
-        d->dcap2 = d->d_D2 ? doubles : 0;
-        if (!d->d_D2) MFAIL(d, "out of device memory (distance matrix of the samples ahead)");
-    }
-    return 0;
+    return grow_scratch(d, &d->d_D2, &d->dcap2, doubles, "distance matrix of the samples ahead");
 }
 
 /* enqueue, on the generator's stream, the sampling of the iteration AFTER the current one: rows npts .. npts + N - 1 (the current
@@ -281,38 +360,27 @@ static int ahead_buffers(mlsl_dev *d, size_t doubles)
  * pts_update_newpt: mlsl.c:155-178) and their closest_lm_d over the minima known now (find_closest_lm, :139-153).  Called in front of
  * the local searches' launch, behind the generator's fill of the words these rows are made of.  Every allocation it may need is
  * made here, before anything is enqueued (freeing device memory waits for the whole device). */
-static int mlsl_enqueue_ahead(mlsl_dev *d, int n)
+static int mlsl_enqueue_ahead(mlsl_dev *d)
 {
     const size_t old = d->npts, nlms = d->nlms;
     const int N = d->N, nb = (int) (old + (size_t) N);
     const size_t cols = (size_t) nb > nlms ? (size_t) nb : nlms;
-    const double *A, *FA;
     d->ahead_valid = 0;
     if (d->d_V && (uint64_t) d->sobol_next + (uint64_t) N >= 4294967295ULL) return 0;     /* (the iteration itself reports the exhausted sequence) */
     if ((size_t) N * cols > ((size_t) 1 << 29)) { d->ahead = 0; return 0; }               /* a second distance matrix above 4 GiB: not worth the memory */
     if (grow_pts(d, old + (size_t) N) || ahead_buffers(d, (size_t) N * cols)) return -1;
-    A = d->d_P + old * (size_t) d->ld; FA = d->d_F + old;
     if (d->h_gate_gave_up && *(volatile int32_t *) d->h_gate_gave_up) {     /* (the launch it belonged to has long ended) */
         *(volatile int32_t *) d->h_gate_gave_up = 0; d->gate_off = 1;
         if (d->stats) ++d->stats->mlsl_gate_timeouts;
     }
     if (d->gate_need > 0 && !d->gate_off && nla_k_gate(d->gate_counter, d->gate_from, d->gate_need, 50.0, d->h_gate_gave_up, d->rs)) MFAIL(d, "sampling ahead failed");
-    if (d->d_V) {
-        if (nla_k_mlsl_sobol_rows(n, d->ld, d->d_lb, d->d_ub, d->d_V, d->sobol_next, N, d->d_P + old * (size_t) d->ld, d->rs) ||
-            nla_k_eval(d->obj, n, d->ld, A, N, d->d_F + old, d->rs) ||
-            (d->ev.sign < 0 && nla_k_mlsl_negate(d->d_F + old, N, d->rs))) MFAIL(d, "sampling ahead failed");
-    } else if (nla_k_crs_init_rows(d->obj, n, d->ld, d->d_lb, d->d_ub, d->d_words, (int64_t) old, N, d->d_P, d->d_F, d->rs) ||
-               (d->ev.sign < 0 && nla_k_mlsl_negate(d->d_F + old, N, d->rs))) MFAIL(d, "sampling ahead failed");
+    if (mlsl_sample_rows(d, d->rs, old, 1)) MFAIL(d, "sampling ahead failed");
     if (nla_memcpy_d2h(d->Fnew2, d->d_F + old, sizeof(double) * (size_t) N, d->rs) ||
         nla_memcpy_h2d(d->d_cpd2, d->h_inf, sizeof(double) * (size_t) nb, d->rs) ||
-        nla_k_mlsl_dist2(n, d->ld, A, N, d->d_P, nb, d->d_D2, d->rs) ||
-        nla_k_mlsl_rowmin(d->d_D2, nb, N, nb, FA, d->d_F, NULL, d->d_cpd2 + old, d->rs) ||
-        nla_k_mlsl_colmin(d->d_D2, nb, N, (int) old, FA, d->d_F, NULL, d->d_cpd2, d->rs) ||
-        nla_memcpy_d2h(d->h_cpd2, d->d_cpd2, sizeof(double) * (size_t) nb, d->rs)) MFAIL(d, "distance pass ahead failed");
-    if (nlms && (nla_k_mlsl_dist2(n, d->ld, A, N, d->d_LM, (int) nlms, d->d_D2, d->rs) ||
-                 nla_k_mlsl_rowmin(d->d_D2, (int) nlms, N, (int) nlms, FA, d->d_LF, NULL, d->d_cld2, d->rs) ||
-                 nla_memcpy_d2h(d->h_cld2, d->d_cld2, sizeof(double) * (size_t) N, d->rs))) MFAIL(d, "distance pass ahead failed");
-    if (nla_event_record(d->ev_ahead, d->rs)) MFAIL(d, "distance pass ahead failed");
+        mlsl_closest_pt_pass(d, d->rs, old, 0, N, d->d_D2, d->d_cpd2, NULL) ||
+        nla_memcpy_d2h(d->h_cpd2, d->d_cpd2, sizeof(double) * (size_t) nb, d->rs) ||
+        mlsl_closest_lm_pass(d, d->rs, old, 0, N, 0, nlms, d->d_D2, d->d_cld2, d->h_cld2) ||
+        nla_event_record(d->ev_ahead, d->rs)) MFAIL(d, "distance pass ahead failed");
     d->ahead_old = old; d->ahead_nlms = nlms; d->ahead_words = d->words_used; d->ahead_sobol = d->sobol_next;
     d->ahead_valid = 1;
     return 0;
@@ -365,14 +433,14 @@ static void ord_insert_run(size_t *ord, size_t cnt, const double *F, size_t firs
 
 /* the distances of a batch's minimisers to every point + the nb x nb of them the commit walk reads, enqueued on the stream (MLSL's
  * local phase; with a device objective on one rank: right behind the searches' kernel, nla_local_ctx_after_launch) */
-typedef struct { mlsl_dev *d; int n, nb; size_t na; const double *ctx_X; size_t lx_bytes; } mlsl_pairs_job;
+typedef struct { mlsl_dev *d; int nb; size_t na; const double *ctx_X; size_t lx_bytes; } mlsl_pairs_job;
 static int mlsl_enqueue_pairs(void *arg)
 {
     mlsl_pairs_job *j = (mlsl_pairs_job *) arg;
     mlsl_dev *d = j->d;
     if (j->ctx_X && j->lx_bytes && nla_memcpy_d2d(d->d_LX, j->ctx_X, j->lx_bytes, d->st)) return -1;      /* (one rank: the all-gather of the minimisers is this copy) */
     return nla_memcpy_h2d(d->d_gi, d->h_gi, sizeof(int64_t) * (size_t) j->nb, d->st) ||
-           nla_k_mlsl_dist2(j->n, d->ld, d->d_LX, (int) j->na, d->d_P, (int) d->npts, d->d_D, d->st) ||
+           nla_k_mlsl_dist2(d->n, d->ld, d->d_LX, (int) j->na, d->d_P, (int) d->npts, d->d_D, d->st) ||
            nla_k_mlsl_gather_pairs_t(d->d_D, (int) d->npts, d->d_gi, j->nb, d->d_idx, j->nb, d->d_S, d->st) ||
            nla_memcpy_d2h(d->h_S, d->d_S, sizeof(double) * (size_t) j->nb * (size_t) j->nb, d->st);
 }
@@ -398,8 +466,7 @@ static int min_over_ranks(mlsl_dev *d, double *v, size_t count)
     return 0;
 }
 
-/* the objective as MLSL's local optimiser sees it (fcount, mlsl.c:246-251): every call counted where the caller can see it */
-typedef struct { nlopt_func f; void *f_data; double sign; int *nevals_p; } mlsl_count_wrap;
+/* the objective as MLSL's local optimiser sees it (mlsl_count_wrap) */
 static double mlsl_counted_f(unsigned n, const double *x, double *grad, void *p)
 {
     mlsl_count_wrap *w = (mlsl_count_wrap *) p;
@@ -414,93 +481,175 @@ static double mlsl_signed_f(unsigned n, const double *x, double *grad, void *p)
     return w->sign * w->f(n, x, NULL, w->f_data);
 }
 
-nlopt_result nla_mlsl_minimize(nlopt_opt opt, int n, nlopt_func f, void *f_data, const double *lb, const double *ub, double *x,
-                               double *minf, nla_stopping *stop, nlopt_opt local_opt, int Nsamples, int lds)
-{
-    mlsl_dev D;
-    nlopt_result ret = NLOPT_SUCCESS;
-    nlopt_amd_stats *st = opt ? &opt->stats : NULL;
-    nla_lbfgs_params prm;
-    nla_lbfgs_result *res = NULL, *res_mine = NULL;
-    size_t *cand = NULL;
-    int bmax;
-    double R_prefactor, *Fnew = NULL, best_f = HUGE_VAL;
-    const double dlm = 1.0, dbound = 1e-6;
-    const double *lbh = lb, *ubh = ub;
-    int i, mf, best_is_lm = 0, loc_maxeval, use_mma = 0, use_cobyla = 0, cob_dev = 0, host, batch;
-    mlsl_count_wrap cw, sw;
-    nlopt_func lo_f = NULL; void *lo_fdata = NULL;
-    nla_mma_params mma;
-    nla_stopping lstop, agreed_view;
-    const nla_stopping *sp = stop;
-    int agreed_force = 0;
-    size_t best_row = 0;
-    double *cob_x = NULL;
 
-    memset(&D, 0, sizeof D);
-    D.N = Nsamples ? Nsamples : 4;                                             /* mlsl.c:283-286 */
-    if (D.N < 1) { nla_stop_msg(stop, "population %d is too small", D.N); return NLOPT_INVALID_ARGS; }
+/* ---- small pieces every phase uses ---- */
+static const double dlm = 1.0, dbound = 1e-6;             /* mlsl.c:324-325 */
+
+/* candidate c of a batch is minimised by rank c mod world in its slot c / world (`per` slots per rank): its gathered row */
+static inline size_t mlsl_gi(int c, int world, int per) { return (size_t) (c % world) * (size_t) per + (size_t) (c / world); }
+
+static int mlsl_agree(mlsl_dev *d)
+{
+    d->sp = nla_comm_agree_stop(d->comm, d->stop, &d->agreed_view, &d->agreed_force);
+    if (!d->sp) MFAIL(d, "stop agreement failed: %s", nlopt_amd_comm_error(d->comm));
+    return 0;
+}
+
+/* The three stop-test sequences differ in order ON PURPOSE: each restates the reference's lines named with it.
+ * After a sample (mlsl.c:340-343 for the first point, :365-368): forced, evals, time, minf */
+static nlopt_result mlsl_stop_after_sample(const mlsl_dev *d, double fv)
+{
+    if (nla_stop_forced(d->sp)) return NLOPT_FORCED_STOP;
+    if (nla_stop_evals(d->stop)) return NLOPT_MAXEVAL_REACHED;
+    if (nla_stop_time(d->sp)) return NLOPT_MAXTIME_REACHED;
+    if (fv < d->stop->minf_max) return NLOPT_MINF_MAX_REACHED;
+    return NLOPT_SUCCESS;
+}
+/* after a local search, when its minimum is committed (mlsl.c:413-419): forced, minf, evals, time */
+static nlopt_result mlsl_stop_after_search(const mlsl_dev *d, double lf)
+{
+    if (nla_stop_forced(d->sp)) return NLOPT_FORCED_STOP;
+    if (lf < d->stop->minf_max) return NLOPT_MINF_MAX_REACHED;
+    if (nla_stop_evals(d->stop)) return NLOPT_MAXEVAL_REACHED;
+    if (nla_stop_time(d->sp)) return NLOPT_MAXTIME_REACHED;
+    return NLOPT_SUCCESS;
+}
+/* in front of a search whose callbacks the caller sees (mlsl.c:391-399; one process): forced, evals, and the raw clock of the
+ * caller's own `stop`, not of the agreed view */
+static nlopt_result mlsl_stop_before_host_search(const mlsl_dev *d)
+{
+    const nla_stopping *stop = d->stop;
+    if (nla_stop_forced(stop)) return NLOPT_FORCED_STOP;
+    if (nla_stop_evals(stop)) return NLOPT_MAXEVAL_REACHED;
+    if (stop->maxtime > 0 && nla_seconds() - stop->start >= stop->maxtime) return NLOPT_MAXTIME_REACHED;
+    return NLOPT_SUCCESS;
+}
+
+/* the evaluation limit of the next local search (nlopt_optimize_limited, optimize.c:1097-1100) */
+static int mlsl_eval_limit(const mlsl_dev *d)
+{
+    const long limited = (long) d->stop->maxeval - (long) *d->stop->nevals_p;
+    int eff = d->loc_maxeval;
+    if (d->loc_maxeval <= 0 || (limited > 0 && limited < d->loc_maxeval)) eff = (int) limited;
+    return eff;
+}
+
+static void mlsl_trace(nlopt_opt opt, double f, size_t row, int kind, int accepted)
+{
+    if (!opt || !opt->trace) return;
+    if (opt->trace_len < opt->trace_cap) { nlopt_amd_trace_rec *tr = opt->trace + opt->trace_len; tr->f = f; tr->row = (int64_t) row; tr->kind = kind; tr->accepted = accepted; }
+    ++opt->trace_len;
+}
+
+static void mlsl_get_minf(mlsl_dev *d)                                         /* get_minf, mlsl.c:258-274 */
+{
+    if (d->npts) { d->best_f = d->F[d->ord[0]]; d->best_row = d->ord[0]; d->best_is_lm = 0; }
+    if (d->nlms && d->LF[d->lord[0]] < d->best_f) { d->best_f = d->LF[d->lord[0]]; d->best_row = d->lord[0]; d->best_is_lm = 1; }
+}
+
+/* what waits for the next launch of local searches (see the end of mlsl_sampling_phase): the generator's fill of the next iteration's
+ * words, and that iteration's sampling phase behind it */
+static int mlsl_prefetch_now(mlsl_dev *d)
+{
+    if (d->prefetch_due) {
+        d->prefetch_due = 0;
+        if (nla_mtstream_fill(d->mts, d->words_used, 2ULL * (uint64_t) d->n * (uint64_t) d->N, d->d_words)) MFAIL(d, "MT stream fill failed");
+        d->prefetched_at = d->words_used;
+    }
+    if (d->ahead_due) { d->ahead_due = 0; if (mlsl_enqueue_ahead(d)) return -1; }
+    return 0;
+}
+
+/* ---- set-up ---- */
+
+/* the arguments the reference checks (mlsl.c:283-297), and the local optimisers this library provides */
+static nlopt_result mlsl_check_args(mlsl_dev *d, nla_stopping *stop, nlopt_opt local_opt, int Nsamples)
+{
+    int rc;
+    d->N = Nsamples ? Nsamples : 4;                                            /* mlsl.c:283-286 */
+    if (d->N < 1) { nla_stop_msg(stop, "population %d is too small", d->N); return NLOPT_INVALID_ARGS; }
     if (!local_opt || (local_opt->algorithm != NLOPT_LD_LBFGS && local_opt->algorithm != NLOPT_LD_MMA && local_opt->algorithm != NLOPT_LN_COBYLA)) {
         nla_stop_msg(stop, "nlopt_amd: MLSL is provided with NLOPT_LD_LBFGS, NLOPT_LD_MMA or NLOPT_LN_COBYLA as the local optimizer only (not %s)",
                      local_opt ? nlopt_algorithm_name(local_opt->algorithm) : "none");
         return NLOPT_INVALID_ARGS;
     }
-    use_mma = local_opt->algorithm == NLOPT_LD_MMA;
-    /* LN_COBYLA (GN_MLSL's default, optimize.c:763-768).  With a compiled-in device objective (round 6) the searches of a batch run
-     * CONCURRENTLY on the device, one wavefront per start, like LD_LBFGS / LD_MMA: `cob_dev`.  The search's whole state is in LDS while
-     * it fits a compute unit's (n <= 51, hip/cobyla_kernels.hip); beyond, up to NLA_COBYLA_GLOBAL_MAX_N, its matrices are in device
-     * memory (hip/cobyla_global.hip) — the same search, local_ctx.c picks the launcher.  With a user-supplied device objective
-     * (NLA_EVAL_USER) on one process, n <= NLA_COBYLA_GLOBAL_MAX_N, the same again as a coroutine (hip/cobyla_ext.hip): the waiting
-     * searches of a batch are evaluated by ONE launch of the user's kernel per step (nla_local_ctx_run), and everything behind
-     * `cob_dev` is the compiled-in case's.  Otherwise — a host callback, a user kernel on several ranks (nothing there to check it
-     * against), a dimension beyond the kernels (or a device layer without them), or "amd_cobyla_host" = 1 — it is a HOST algorithm
-     * (cobyla_host.c): the searches run one at a time on the caller's thread through the library's own nlopt_optimize, exactly as
-     * mlsl.c:404-407 runs them; samples, distances and the bookkeeping stay on the device, and the run takes the host-callback path
-     * throughout. */
-    use_cobyla = local_opt->algorithm == NLOPT_LN_COBYLA;
-    if (use_mma && (i = nla_mma_read_params(local_opt, &mma))) {
+    if (local_opt->algorithm == NLOPT_LD_MMA && (rc = nla_mma_read_params(local_opt, &d->mma))) {
         nla_stop_msg(stop, "%s", local_opt->errmsg ? local_opt->errmsg : "invalid LD_MMA parameter");
-        return (nlopt_result) i;
+        return (nlopt_result) rc;
     }
-    if (nla_dev_count() <= 0) {
-        nla_stop_msg(stop, "nlopt_amd: no HIP device visible (this library has no CPU fallback)");
-        nla_comm_agree_ready((opt && !use_cobyla) ? opt->comm : NULL, 0);
-        return NLOPT_FAILURE;
-    }
-    nla_evaluator_resolve(&D.ev, opt, f, f_data);
-    D.obj = D.ev.kind == NLA_EVAL_DEVICE ? D.ev.obj : -1;
-    cob_dev = use_cobyla && nla_cobyla_device_serves(D.ev.kind, n) && (D.ev.kind == NLA_EVAL_DEVICE || nlopt_amd_comm_world(opt ? opt->comm : NULL) == 1) &&
-              !(opt && nlopt_get_param(opt, "amd_cobyla_host", 0) != 0) && !nlopt_get_param(local_opt, "amd_cobyla_host", 0);
+    return NLOPT_SUCCESS;
+}
+
+/* Who runs the local searches (d->ev is resolved).  LD_LBFGS and LD_MMA: their batched kernels.
+ * LN_COBYLA (GN_MLSL's default, optimize.c:763-768).  With a compiled-in device objective (round 6) the searches of a batch run
+ * CONCURRENTLY on the device, one wavefront per start, like LD_LBFGS / LD_MMA: MLSL_DEV_COBYLA.  The search's whole state is in LDS while
+ * it fits a compute unit's (n <= 51, hip/cobyla_kernels.hip); beyond, up to NLA_COBYLA_GLOBAL_MAX_N, its matrices are in device
+ * memory (hip/cobyla_global.hip) — the same search, local_ctx.c picks the launcher.  With a user-supplied device objective
+ * (NLA_EVAL_USER) on one process, n <= NLA_COBYLA_GLOBAL_MAX_N, the same again as a coroutine (hip/cobyla_ext.hip): the waiting
+ * searches of a batch are evaluated by ONE launch of the user's kernel per step (nla_local_ctx_run), and everything else
+ * is the compiled-in case's.  Otherwise — a host callback, a user kernel on several ranks (nothing there to check it
+ * against), a dimension beyond the kernels (or a device layer without them), or "amd_cobyla_host" = 1 on either object — it is a HOST
+ * algorithm (cobyla_host.c), MLSL_HOST_SEARCH: the searches run one at a time on the caller's thread through the library's own
+ * nlopt_optimize, exactly as mlsl.c:404-407 runs them; samples, distances and the bookkeeping stay on the device, and the run takes the
+ * host-callback path throughout. */
+static mlsl_local mlsl_choose_local(const mlsl_dev *d, nlopt_opt opt, nlopt_opt local_opt, const double *lb, const double *ub)
+{
+    int i, dev;
+    if (local_opt->algorithm == NLOPT_LD_MMA) return MLSL_MMA;
+    if (local_opt->algorithm != NLOPT_LN_COBYLA) return MLSL_LBFGS;
+    dev = nla_cobyla_device_serves(d->ev.kind, d->n) && (d->ev.kind == NLA_EVAL_DEVICE || nlopt_amd_comm_world(opt ? opt->comm : NULL) == 1) &&
+          !(opt && nlopt_get_param(opt, "amd_cobyla_host", 0) != 0) && !nlopt_get_param(local_opt, "amd_cobyla_host", 0);
     /* a fixed coordinate (lb[i] == ub[i]): the reference's nlopt_optimize_limited eliminates it in front of each COBYLA search
      * (optimize.c:412-445), the device kernel does not (it refuses such a box, include/nlopt_amd.h) — the host algorithm, whose
      * nlopt_optimize eliminates like the reference (api_optimize.c fix_applies) */
-    for (i = 0; cob_dev && i < n; ++i) if (lb[i] == ub[i]) cob_dev = 0;
-    if (cob_dev) use_cobyla = 0;              /* from here on `use_cobyla` means: the host algorithm */
-    host = D.ev.kind == NLA_EVAL_HOST || use_cobyla;
-    sw.f = f; sw.f_data = f_data; sw.sign = -1.; sw.nevals_p = NULL;
-    if (use_cobyla && D.ev.kind != NLA_EVAL_HOST && D.ev.sign < 0) { f = mlsl_signed_f; f_data = &sw; }   /* a maximisation the dispatcher left unflipped (dev_sign): flip here */
-    D.n = n; D.ld = (n + 1) & ~1;
-    D.comm = (opt && !use_cobyla) ? opt->comm : NULL;              /* host searches: every rank runs the identical job, nothing to exchange */
-    D.world = nlopt_amd_comm_world(D.comm); D.rank = nlopt_amd_comm_rank(D.comm);
-    batch = host ? 1 : BATCH_MAX;             /* a host callback is called for one search at a time, in the reference's order */
-    bmax = (host ? 1 : BATCH_MAX) * D.world;
+    for (i = 0; dev && i < d->n; ++i) if (lb[i] == ub[i]) dev = 0;
+    return dev ? MLSL_DEV_COBYLA : MLSL_HOST_SEARCH;
+}
+
+/* Everything a run needs before its first evaluation.  ONE failure exit: the message, "not ready" to the other ranks (several ranks:
+ * set-up ends with an exchange of "ready" — comm.c, nla_comm_agree_ready — and a rank that fails here says so there instead of
+ * leaving the others in the run's first collective), the result code.  The caller tears down (mfree) whatever was made. */
+static nlopt_result mlsl_setup(mlsl_dev *d, nlopt_opt opt, int n, nlopt_func f, void *f_data, const double *lb, const double *ub,
+                               nla_stopping *stop, nlopt_opt local_opt, int lds)
+{
+    const char *msg = "nlopt_amd: could not create the MLSL device state";
+    nlopt_result code = NLOPT_OUT_OF_MEMORY;
+    nlopt_amd_stats *st = opt ? &opt->stats : NULL;
+    int i, bmax;
+
+    d->opt = opt; d->local_opt = local_opt; d->stop = stop; d->sp = stop; d->stats = st;
+    d->n = n; d->ld = (n + 1) & ~1;
+    if (nla_dev_count() <= 0) {
+        /* (asked before the searches are placed: with LN_COBYLA, host or device, this exit has never told the other ranks) */
+        d->comm = (opt && local_opt->algorithm != NLOPT_LN_COBYLA) ? opt->comm : NULL;
+        msg = "nlopt_amd: no HIP device visible (this library has no CPU fallback)"; code = NLOPT_FAILURE;
+        goto fail;
+    }
+    nla_evaluator_resolve(&d->ev, opt, f, f_data);
+    d->obj = d->ev.kind == NLA_EVAL_DEVICE ? d->ev.obj : -1;
+    d->local = mlsl_choose_local(d, opt, local_opt, lb, ub);
+    d->host = d->ev.kind == NLA_EVAL_HOST || d->local == MLSL_HOST_SEARCH;
+    d->sw.f = f; d->sw.f_data = f_data; d->sw.sign = -1.; d->sw.nevals_p = NULL;
+    if (d->local == MLSL_HOST_SEARCH && d->ev.kind != NLA_EVAL_HOST && d->ev.sign < 0) { f = mlsl_signed_f; f_data = &d->sw; }   /* a maximisation the dispatcher left unflipped (dev_sign): flip here */
+    d->f = f; d->f_data = f_data;
+    d->comm = (opt && d->local != MLSL_HOST_SEARCH) ? opt->comm : NULL;       /* host searches: every rank runs the identical job, nothing to exchange */
+    d->world = nlopt_amd_comm_world(d->comm); d->rank = nlopt_amd_comm_rank(d->comm);
+    d->batch = d->host ? 1 : BATCH_MAX;       /* a host callback is called for one search at a time, in the reference's order */
+    d->bmax = bmax = d->batch * d->world;
     /* what a local search observes of the caller's stopping state: the force_stop flag and the run's clock
      * (nlopt_optimize_limited hands the remaining time down, optimize.c:1101-1104) */
-    lstop = *stop;
-    lstop.xtol_abs = local_opt->xtol_abs; lstop.x_weights = local_opt->x_weights;
-    R_prefactor = sqrt(2. / K2PI) * pow(gam(n) * MLSL_SIGMA, 1.0 / n);            /* mlsl.c:313-317 */
-    for (i = 0; i < n; ++i) R_prefactor *= pow(ub[i] - lb[i], 1.0 / n);
+    d->lstop = *stop;
+    d->lstop.xtol_abs = local_opt->xtol_abs; d->lstop.x_weights = local_opt->x_weights;
+    d->R_prefactor = sqrt(2. / K2PI) * pow(gam(n) * MLSL_SIGMA, 1.0 / n);        /* mlsl.c:313-317 */
+    for (i = 0; i < n; ++i) d->R_prefactor *= pow(ub[i] - lb[i], 1.0 / n);
+    d->best_f = HUGE_VAL;
 
     /* the local optimiser as nlopt_optimize_limited(local_opt, ...) would configure it (mlsl.c:303-306,404-407) */
-    memset(&prm, 0, sizeof prm);
-    prm.minf_max = stop->minf_max; prm.ftol_rel = local_opt->ftol_rel; prm.ftol_abs = local_opt->ftol_abs;
-    prm.xtol_rel = local_opt->xtol_rel; prm.tolg = nlopt_get_param(local_opt, "tolg", 0.);
-    loc_maxeval = local_opt->maxeval;
-    mf = nla_lbfgs_default_mf(n, (int) local_opt->vector_storage, 0);
+    d->prm.minf_max = stop->minf_max; d->prm.ftol_rel = local_opt->ftol_rel; d->prm.ftol_abs = local_opt->ftol_abs;
+    d->prm.xtol_rel = local_opt->xtol_rel; d->prm.tolg = nlopt_get_param(local_opt, "tolg", 0.);
+    d->loc_maxeval = local_opt->maxeval;
 
-    D.st = nla_stream_create();
-    /* several ranks: set-up ends with an exchange of "ready" (comm.c, nla_comm_agree_ready) — a rank that fails below says so there
-     * instead of leaving the others in the run's first collective */
+    d->st = nla_stream_create();
     /* PREFETCH (always, with a device objective; measured on the MI355X in round 5 together with the short segments below: config 4
      * 15.9 -> 13.9 ms per iteration, profiles/r05_staged_ab.txt): pseudo-random sampling (every MLSL
      * variant at n > 1111, where the reference has no Sobol generator either) costs a generator pass per iteration that is bound by
@@ -508,470 +657,530 @@ nlopt_result nla_mlsl_minimize(nlopt_opt opt, int n, nlopt_func f, void *f_data,
      * 7.5 ms sampling phase.  Nothing between two sampling phases draws random numbers (the local optimisers are deterministic), so
      * the NEXT iteration's words are generated on a stream of their own beside the distance pass and the local searches.  Hand-over
      * = a host synchronisation of that stream before the sampling kernel reads them. */
-    D.prefetch = !host;
+    d->prefetch = !d->host;
     /* (not with the sums in the reference's order, amd_exact_dot = 1: that launch is one chain of dependent fp64 additions per search,
      * every issue slot the distance pass takes on its SIMD delays the chain — measured: 103 -> 117 ms per launch, round 5) */
-    D.ahead = !host && D.world == 1 && D.ev.kind == NLA_EVAL_DEVICE && !use_cobyla && !cob_dev && !nla_exact_mode_for(opt, local_opt, &D.ev);
-    D.prefetched_at = ~0ULL;
-    D.stats = st;
-    if (D.ahead) { D.h_gate_gave_up = (int32_t *) nla_host_malloc(sizeof(int32_t)); if (D.h_gate_gave_up) *D.h_gate_gave_up = 0; }     /* (its failure is the set-up's, below) */
-    D.rs = (D.st && D.prefetch) ? nla_stream_create_background() : D.st;
-    D.ev_samples = nla_event_create();
-    D.ev_ahead = nla_event_create();
+    d->ahead = !d->host && d->world == 1 && d->ev.kind == NLA_EVAL_DEVICE && d->local != MLSL_DEV_COBYLA && !nla_exact_mode_for(opt, local_opt, &d->ev);
+    d->prefetched_at = ~0ULL;
+    if (d->ahead) { d->h_gate_gave_up = (int32_t *) nla_host_malloc(sizeof(int32_t)); if (d->h_gate_gave_up) *d->h_gate_gave_up = 0; }     /* (its failure is found below) */
+    d->rs = (d->st && d->prefetch) ? nla_stream_create_background() : d->st;
+    d->ev_samples = nla_event_create();
+    d->ev_ahead = nla_event_create();
     {
         /* "amd_mlsl_seg_regens": the segment length of this run's stream (NLA_MT_SEG_REGENS = 1024 is the layout every other algorithm
          * uses) — 64 makes 205 wavefronts of the 13 above; measured at config 4 (MI355X, round 5): 15.9 ms per iteration at 1024, 14.7 at
          * 256, 14.4 at 64, 14.3 at 16.  The words are the same. */
         int seg = opt ? (int) nlopt_get_param(opt, "amd_mlsl_seg_regens", NLA_MLSL_SEG_REGENS) : NLA_MLSL_SEG_REGENS;
         if (seg < 1 || seg > NLA_MT_SEG_REGENS || (seg & (seg - 1))) seg = NLA_MT_SEG_REGENS;
-        if (D.st && D.rs) D.mts = seg == NLA_MT_SEG_REGENS ? nla_mtstream_create(D.rs) : nla_mtstream_create_seg(D.rs, seg);
+        if (d->st && d->rs) d->mts = seg == NLA_MT_SEG_REGENS ? nla_mtstream_create(d->rs) : nla_mtstream_create_seg(d->rs, seg);
     }
-    if (!D.st || !D.rs || !D.mts) { nla_stop_msg(stop, "nlopt_amd: could not create the device stream / generator state"); nla_comm_agree_ready(D.comm, 0); mfree(&D); return NLOPT_OUT_OF_MEMORY; }
-    D.d_lb = (double *) nla_dev_malloc(sizeof(double) * (size_t) D.ld);
-    D.d_ub = (double *) nla_dev_malloc(sizeof(double) * (size_t) D.ld);
-    D.d_words = (uint32_t *) nla_dev_malloc(sizeof(uint32_t) * 2 * (size_t) n * (size_t) D.N);
-    D.d_tmp = (double *) nla_dev_malloc(sizeof(double) * (size_t) (D.N > bmax ? D.N : bmax));
-    D.d_LX = (double *) nla_dev_malloc(sizeof(double) * (size_t) bmax * (size_t) D.ld);
-    D.h_idx = (int64_t *) nla_host_malloc(sizeof(int64_t) * (size_t) (2 * bmax + BATCH_MAX));
-    D.d_idx = (int64_t *) nla_dev_malloc(sizeof(int64_t) * (size_t) (2 * bmax + BATCH_MAX));
-    D.h_lf = (double *) nla_host_malloc(sizeof(double) * (size_t) bmax);
-    D.h_S = (double *) nla_host_malloc(sizeof(double) * (size_t) bmax * (size_t) bmax);
-    D.d_S = (double *) nla_dev_malloc(sizeof(double) * (size_t) bmax * (size_t) bmax);
-    D.h_lfall = (double *) nla_host_malloc(sizeof(double) * (size_t) bmax);
-    D.lf_cand = (double *) malloc(sizeof(double) * (size_t) bmax);
-    D.d_lfall = (double *) nla_dev_malloc(sizeof(double) * (size_t) bmax);
-    D.h_gi = (int64_t *) nla_host_malloc(sizeof(int64_t) * (size_t) bmax);
-    D.d_gi = (int64_t *) nla_dev_malloc(sizeof(int64_t) * (size_t) bmax);
-    D.h_flags = (int32_t *) nla_host_malloc(sizeof(int32_t) * (size_t) bmax);
-    D.d_flags = (int32_t *) nla_dev_malloc(sizeof(int32_t) * (size_t) bmax);
-    Fnew = (double *) nla_host_malloc(sizeof(double) * (size_t) D.N);        /* pinned: the samples' values come back every iteration */
-    if (host) D.h_rows = (double *) nla_host_malloc(sizeof(double) * (size_t) D.N * (size_t) D.ld);
-    res = (nla_lbfgs_result *) malloc(sizeof *res * (size_t) bmax);
-    res_mine = (nla_lbfgs_result *) calloc(BATCH_MAX, sizeof *res_mine);
-    cand = (size_t *) malloc(sizeof *cand * (size_t) bmax);
-    if ((host && !D.h_rows) || !D.h_idx || !D.d_idx || !D.h_lf || !D.h_S || !D.d_S || !D.h_lfall || !D.lf_cand || !D.d_lfall || !D.h_gi || !D.d_gi || !D.h_flags || !D.d_flags || !D.d_lb || !D.d_ub || !D.d_words || !D.d_tmp || !D.d_LX || !D.ev_samples || !D.ev_ahead || (D.ahead && !D.h_gate_gave_up) || !Fnew || !res || !res_mine || !cand || grow_pts(&D, (size_t) D.N + 1) || grow_lms(&D, 1) ||
-        nla_memcpy_h2d(D.d_lb, lbh, sizeof(double) * (size_t) n, D.st) || nla_memcpy_h2d(D.d_ub, ubh, sizeof(double) * (size_t) n, D.st)) {
-        nla_stop_msg(stop, "nlopt_amd: could not create the MLSL device state");
-        nla_comm_agree_ready(D.comm, 0);
-        mfree(&D); nla_host_free(Fnew); free(res); free(res_mine); free(cand);
-        return NLOPT_OUT_OF_MEMORY;
-    }
+    if (!d->st || !d->rs || !d->mts) { msg = "nlopt_amd: could not create the device stream / generator state"; goto fail; }
+    d->d_lb = (double *) nla_dev_malloc(sizeof(double) * (size_t) d->ld);
+    d->d_ub = (double *) nla_dev_malloc(sizeof(double) * (size_t) d->ld);
+    d->d_words = (uint32_t *) nla_dev_malloc(sizeof(uint32_t) * 2 * (size_t) n * (size_t) d->N);
+    d->d_tmp = (double *) nla_dev_malloc(sizeof(double) * (size_t) (d->N > bmax ? d->N : bmax));
+    d->d_LX = (double *) nla_dev_malloc(sizeof(double) * (size_t) bmax * (size_t) d->ld);
+    d->h_idx = (int64_t *) nla_host_malloc(sizeof(int64_t) * (size_t) (2 * bmax + BATCH_MAX));
+    d->d_idx = (int64_t *) nla_dev_malloc(sizeof(int64_t) * (size_t) (2 * bmax + BATCH_MAX));
+    d->h_lf = (double *) nla_host_malloc(sizeof(double) * (size_t) bmax);
+    d->h_S = (double *) nla_host_malloc(sizeof(double) * (size_t) bmax * (size_t) bmax);
+    d->d_S = (double *) nla_dev_malloc(sizeof(double) * (size_t) bmax * (size_t) bmax);
+    d->h_lfall = (double *) nla_host_malloc(sizeof(double) * (size_t) bmax);
+    d->lf_cand = (double *) malloc(sizeof(double) * (size_t) bmax);
+    d->d_lfall = (double *) nla_dev_malloc(sizeof(double) * (size_t) bmax);
+    d->h_gi = (int64_t *) nla_host_malloc(sizeof(int64_t) * (size_t) bmax);
+    d->d_gi = (int64_t *) nla_dev_malloc(sizeof(int64_t) * (size_t) bmax);
+    d->h_flags = (int32_t *) nla_host_malloc(sizeof(int32_t) * (size_t) bmax);
+    d->d_flags = (int32_t *) nla_dev_malloc(sizeof(int32_t) * (size_t) bmax);
+    d->Fnew = (double *) nla_host_malloc(sizeof(double) * (size_t) d->N);
+    if (d->host) d->h_rows = (double *) nla_host_malloc(sizeof(double) * (size_t) d->N * (size_t) d->ld);
+    d->res = (nla_lbfgs_result *) malloc(sizeof *d->res * (size_t) bmax);
+    d->res_mine = (nla_lbfgs_result *) calloc(BATCH_MAX, sizeof *d->res_mine);
+    d->cand = (size_t *) malloc(sizeof *d->cand * (size_t) bmax);
+    if ((d->host && !d->h_rows) || !d->h_idx || !d->d_idx || !d->h_lf || !d->h_S || !d->d_S || !d->h_lfall || !d->lf_cand || !d->d_lfall || !d->h_gi || !d->d_gi ||
+        !d->h_flags || !d->d_flags || !d->d_lb || !d->d_ub || !d->d_words || !d->d_tmp || !d->d_LX || !d->ev_samples || !d->ev_ahead || (d->ahead && !d->h_gate_gave_up) ||
+        !d->Fnew || !d->res || !d->res_mine || !d->cand || grow_pts(d, (size_t) d->N + 1) || grow_lms(d, 1) ||
+        nla_memcpy_h2d(d->d_lb, lb, sizeof(double) * (size_t) n, d->st) || nla_memcpy_h2d(d->d_ub, ub, sizeof(double) * (size_t) n, d->st)) goto fail;
     if (lds) {                                                                 /* d.s = nlopt_sobol_create(n), mlsl.c:306 */
         uint32_t *V = (uint32_t *) malloc(sizeof(uint32_t) * 32 * (size_t) n);
+        int bad = 0;
         if (V && nla_sobol_directions((unsigned) n, V)) {
-            D.d_V = (uint32_t *) nla_dev_malloc(sizeof(uint32_t) * 32 * (size_t) n);
-            if (!D.d_V || nla_memcpy_h2d(D.d_V, V, sizeof(uint32_t) * 32 * (size_t) n, D.st) || nla_stream_sync(D.st)) {
-                nla_stop_msg(stop, "nlopt_amd: could not create the MLSL device state");
-                nla_comm_agree_ready(D.comm, 0);
-                free(V); mfree(&D); nla_host_free(Fnew); free(res); free(res_mine); free(cand);
-                return NLOPT_OUT_OF_MEMORY;
-            }
-            D.sobol_next = nla_sobol_skip_count((unsigned) (10 * n + D.N)) + 1;  /* nlopt_sobol_skip(d.s, 10n+N, .), mlsl.c:332 */
+            d->d_V = (uint32_t *) nla_dev_malloc(sizeof(uint32_t) * 32 * (size_t) n);
+            bad = !d->d_V || nla_memcpy_h2d(d->d_V, V, sizeof(uint32_t) * 32 * (size_t) n, d->st) || nla_stream_sync(d->st);
+            d->sobol_next = nla_sobol_skip_count((unsigned) (10 * n + d->N)) + 1;  /* nlopt_sobol_skip(d.s, 10n+N, .), mlsl.c:332 */
         }                                                                      /* else: NULL generator -> nlopt_urand, as the reference */
         free(V);
+        if (bad) goto fail;
     }
-    if ((use_mma || cob_dev) && local_opt->dx) {                                            /* the initial step = MMA's sigma_init, optimize.c:829 */
-        D.d_dx = (double *) nla_dev_malloc(sizeof(double) * (size_t) D.ld);
-        if (!D.d_dx || nla_memcpy_h2d(D.d_dx, local_opt->dx, sizeof(double) * (size_t) n, D.st) || nla_stream_sync(D.st)) {
-            nla_stop_msg(stop, "nlopt_amd: could not create the MLSL device state");
-            nla_comm_agree_ready(D.comm, 0);
-            mfree(&D); nla_host_free(Fnew); free(res); free(res_mine); free(cand);
-            return NLOPT_OUT_OF_MEMORY;
-        }
+    if ((d->local == MLSL_MMA || d->local == MLSL_DEV_COBYLA) && local_opt->dx) {                /* the initial step = MMA's sigma_init, optimize.c:829 */
+        d->d_dx = (double *) nla_dev_malloc(sizeof(double) * (size_t) d->ld);
+        if (!d->d_dx || nla_memcpy_h2d(d->d_dx, local_opt->dx, sizeof(double) * (size_t) n, d->st) || nla_stream_sync(d->st)) goto fail;
     }
-    if (use_cobyla) {
+    if (d->local == MLSL_HOST_SEARCH) {
         /* the local optimiser as mlsl.c:303-306 configures it: counted objective, the box, the stop value */
-        lo_f = local_opt->f; lo_fdata = local_opt->f_data;
-        cw.f = f; cw.f_data = f_data; cw.sign = 1.; cw.nevals_p = stop->nevals_p;      /* (f is already the flipped one where that applies) */
-        /* installed by assignment and taken out again at every exit below (opt->local_opt is the object's own copy whose objective
-         * nlopt_set_local_optimizer cleared, options.c:824-846: nothing of the user's to munge, but nothing of this stack frame
+        d->lo_f = local_opt->f; d->lo_fdata = local_opt->f_data;
+        d->cw.f = f; d->cw.f_data = f_data; d->cw.sign = 1.; d->cw.nevals_p = stop->nevals_p;      /* (f is already the flipped one where that applies) */
+        /* installed by assignment and taken out again by mfree, on every exit (opt->local_opt is the object's own copy whose objective
+         * nlopt_set_local_optimizer cleared, options.c:824-846: nothing of the user's to munge, but nothing of the caller's stack frame
          * may stay behind in it either) */
-        local_opt->f = mlsl_counted_f; local_opt->f_data = &cw; local_opt->pre = NULL; local_opt->maximize = 0;
+        local_opt->f = mlsl_counted_f; local_opt->f_data = &d->cw; local_opt->pre = NULL; local_opt->maximize = 0;
+        d->lo_installed = 1;
         nlopt_set_lower_bounds(local_opt, lb);
         nlopt_set_upper_bounds(local_opt, ub);
         nlopt_set_stopval(local_opt, stop->minf_max);
-        cob_x = (double *) nla_host_malloc(sizeof(double) * (size_t) n);
-        if (!cob_x) { nla_stop_msg(stop, "nlopt_amd: out of pinned memory"); ret = NLOPT_OUT_OF_MEMORY; goto done; }
+        d->cob_x = (double *) nla_host_malloc(sizeof(double) * (size_t) n);
+        if (!d->cob_x) { msg = "nlopt_amd: out of pinned memory"; goto fail; }
     } else {
-    const nla_local_spec spec = { cob_dev ? NLA_LOCAL_COBYLA : use_mma ? NLA_LOCAL_MMA : NLA_LOCAL_LBFGS, &D.ev, n, batch, mf,
-                                  use_mma ? &mma : NULL, D.d_dx, D.d_lb, D.d_ub, D.st };
-    D.lb = nla_local_ctx_create(&spec);
-    if (D.lb && nla_local_ctx_set_options(D.lb, nla_exact_mode_for(opt, local_opt, &D.ev), local_opt->xtol_abs, local_opt->x_weights)) { nla_local_ctx_destroy(D.lb); D.lb = NULL; }
-    /* (LD_LBFGS only: LD_MMA's launches are half as long as the distance pass beside them — behind a gate it ends after them and holds the
-     * next iteration up: config 4 with LD_MMA 8.0 -> 8.3 ms per iteration, profiles/r05_mlsl_ahead_ab.txt) */
-    if (D.lb && D.ahead && !use_mma && NLA_MLSL_GATE_PCT > 0 && nla_local_ctx_count_finished(D.lb)) { nla_local_ctx_destroy(D.lb); D.lb = NULL; }
-    if (!D.lb) { nla_stop_msg(stop, "nlopt_amd: out of device memory (local-search batch)"); nla_comm_agree_ready(D.comm, 0); mfree(&D); nla_host_free(Fnew); free(res); free(res_mine); free(cand); return NLOPT_OUT_OF_MEMORY; }
-    nla_local_ctx_set_stats(D.lb, st);
-    if (cob_dev) nla_local_ctx_set_cobyla_min_batch(D.lb, (int) nlopt_get_param(opt ? opt : local_opt, "amd_cobyla_min_batch", nlopt_get_param(local_opt, "amd_cobyla_min_batch", 0)));
+        const int use_mma = d->local == MLSL_MMA;
+        const nla_local_spec spec = { d->local == MLSL_DEV_COBYLA ? NLA_LOCAL_COBYLA : use_mma ? NLA_LOCAL_MMA : NLA_LOCAL_LBFGS, &d->ev, n, d->batch,
+                                      nla_lbfgs_default_mf(n, (int) local_opt->vector_storage, 0), use_mma ? &d->mma : NULL, d->d_dx, d->d_lb, d->d_ub, d->st };
+        d->lb = nla_local_ctx_create(&spec);
+        if (d->lb && nla_local_ctx_set_options(d->lb, nla_exact_mode_for(opt, local_opt, &d->ev), local_opt->xtol_abs, local_opt->x_weights)) { nla_local_ctx_destroy(d->lb); d->lb = NULL; }
+        /* (LD_LBFGS only: LD_MMA's launches are half as long as the distance pass beside them — behind a gate it ends after them and holds the
+         * next iteration up: config 4 with LD_MMA 8.0 -> 8.3 ms per iteration, profiles/r05_mlsl_ahead_ab.txt) */
+        if (d->lb && d->ahead && !use_mma && NLA_MLSL_GATE_PCT > 0 && nla_local_ctx_count_finished(d->lb)) { nla_local_ctx_destroy(d->lb); d->lb = NULL; }
+        if (!d->lb) { msg = "nlopt_amd: out of device memory (local-search batch)"; goto fail; }
+        nla_local_ctx_set_stats(d->lb, st);
+        if (d->local == MLSL_DEV_COBYLA) nla_local_ctx_set_cobyla_min_batch(d->lb, (int) nlopt_get_param(opt ? opt : local_opt, "amd_cobyla_min_batch", nlopt_get_param(local_opt, "amd_cobyla_min_batch", 0)));
     }
-    if (D.world > 1) {
-        const int all = nla_comm_agree_same(D.comm, 1, nla_problem_fingerprint(lds ? NLOPT_G_MLSL_LDS : NLOPT_G_MLSL, n, D.N, D.obj + 100 * (int) local_opt->algorithm, lb, ub, x, stop) + nla_params_fingerprint(opt) + nla_params_fingerprint(local_opt));
-        if (all < 0) { nla_stop_msg(stop, NLA_MSG_RANKS_DIFFER); ret = NLOPT_INVALID_ARGS; goto done; }
-        if (all == 0) { nla_stop_msg(stop, "nlopt_amd: another rank could not set up its MLSL device state"); ret = NLOPT_FAILURE; goto done; }
-    }
-#define DEVFAIL() do { nla_stop_msg(stop, "device engine: %s", D.err); ret = NLOPT_FAILURE; goto done; } while (0)
-#define PREFETCH_NOW() do { if (prefetch_due) { prefetch_due = 0; \
-        if (nla_mtstream_fill(D.mts, D.words_used, 2ULL * (uint64_t) n * (uint64_t) D.N, D.d_words)) { snprintf(D.err, sizeof D.err, "MT stream fill failed"); DEVFAIL(); } \
-        D.prefetched_at = D.words_used; } \
-    if (ahead_due) { ahead_due = 0; if (mlsl_enqueue_ahead(&D, n)) DEVFAIL(); } } while (0)
+    return NLOPT_SUCCESS;
+fail:
+    nla_stop_msg(stop, "%s", msg);
+    nla_comm_agree_ready(d->comm, 0);
+    return code;
+}
+
+/* ---- the starting guess is the first point (mlsl.c:326-343) ---- */
+static int mlsl_first_point(mlsl_dev *d, const double *x)
+{
+    const size_t xbytes = sizeof(double) * (size_t) d->n;
+    if (d->host) {
+        d->F[0] = d->f((unsigned) d->n, x, NULL, d->f_data);
+        if (nla_memcpy_h2d(d->d_P, x, xbytes, d->st) || nla_memcpy_h2d(d->d_F, d->F, sizeof(double), d->st) ||
+            nla_stream_sync(d->st)) MFAIL(d, "first evaluation failed");
+    } else if (nla_memcpy_h2d(d->d_P, x, xbytes, d->st) || mlsl_eval_rows(d, d->d_P, 1, d->d_F, d->st) ||
+               nla_memcpy_d2h(d->F, d->d_F, sizeof(double), d->st) || nla_stream_sync(d->st)) MFAIL(d, "first evaluation failed");
+    ++*d->stop->nevals_p;
+    d->minimized[0] = 0; d->cpd[0] = HUGE_VAL; d->cld[0] = HUGE_VAL;          /* pts_insert of a fresh point */
+    ord_insert(d->ord, d->npts, d->F, 0);
+    ++d->npts;
+    if (d->F[0] != d->F[0]) d->ord_has_nan = 1;
+    if (mlsl_agree(d)) return -1;
+    d->ret = mlsl_stop_after_sample(d, d->F[0]);
+    return 0;
+}
+
+/* ---- sampling phase (mlsl.c:349-374) ---- */
+
 /* the sampling phase's distance pass (find_closest_pt + pts_update_newpt, find_closest_lm) for the N new points in rows old .. old + N - 1:
  * everything it needs is on the device once the sampling kernel has run — the points, their f, the old points' closest_pt_d and flags
  * (uploaded here: the new rows' entries are set before) — so with a device objective on one rank it is ENQUEUED RIGHT BEHIND THE
  * SAMPLING KERNEL and runs while the host walks the N values (counts, stop tests, the order array: 0.3 ms per iteration that used to
  * stand between the sampling kernel and the distance kernel, profiles/r05_mlsl_timeline.txt).  A run that stops inside that walk
- * leaves; what the pass wrote is not looked at again. */
-#define ENQUEUE_DISTANCES() do { \
-            const int na_ = D.N, nb_ = (int) (old + (size_t) D.N); \
-            const int per_r_ = (na_ + D.world - 1) / D.world; \
-            const int r0_ = per_r_ * D.rank < na_ ? per_r_ * D.rank : na_; \
-            const int mine_r_ = na_ - r0_ < per_r_ ? na_ - r0_ : per_r_; \
-            const double *A_ = D.d_P + (old + (size_t) r0_) * (size_t) D.ld, *FA_ = D.d_F + old + r0_; \
-            if (need_D(&D, (size_t) na_ * (size_t) nb_) || (D.nlms && need_D(&D, (size_t) na_ * D.nlms))) DEVFAIL(); \
-            /* closest_pt_d of the new points: over every point with smaller f; of the old, not yet minimised points: over the new points \
-             * with smaller f.  Several ranks: the ROWS of the new points are dealt in blocks over the ranks; every rank computes its rows' \
-             * minima and its rows' share of the column minima, combined by an element-wise min over an all-gather (exact) */ \
-            if (nla_memcpy_h2d(D.d_cpd, D.cpd, sizeof(double) * (size_t) nb_, D.st) || \
-                nla_memcpy_h2d(D.d_min, D.minimized, sizeof(int32_t) * (size_t) nb_, D.st) || \
-                (mine_r_ > 0 && (nla_k_mlsl_dist2(n, D.ld, A_, mine_r_, D.d_P, nb_, D.d_D, D.st) || \
-                                 nla_k_mlsl_rowmin(D.d_D, nb_, mine_r_, nb_, FA_, D.d_F, NULL, D.d_cpd + old + r0_, D.st) || \
-                                 nla_k_mlsl_colmin(D.d_D, nb_, mine_r_, (int) old, FA_, D.d_F, D.d_min, D.d_cpd, D.st))) || \
-                nla_memcpy_d2h(D.cpd, D.d_cpd, sizeof(double) * (size_t) nb_, D.st)) { snprintf(D.err, sizeof D.err, "distance pass failed"); DEVFAIL(); } \
-            if (D.nlms) {                                                      /* find_closest_lm */ \
-                if (mine_r_ > 0 && (nla_k_mlsl_dist2(n, D.ld, A_, mine_r_, D.d_LM, (int) D.nlms, D.d_D, D.st) || \
-                                    nla_k_mlsl_rowmin(D.d_D, (int) D.nlms, mine_r_, (int) D.nlms, FA_, D.d_LF, NULL, D.d_tmp, D.st) || \
-                                    nla_memcpy_d2h(D.cld + old + r0_, D.d_tmp, sizeof(double) * (size_t) mine_r_, D.st))) { snprintf(D.err, sizeof D.err, "distance pass failed"); DEVFAIL(); } \
-            } \
-            dist_enqueued = 1; } while (0)
-#define NEWPT_UNORDERED(row) do { (void) (row); ++D.npts; } while (0)     /* (entries initialised in front of the walk; ord_insert_run follows) */
-#define NEWPT(row) do { D.minimized[row] = 0; D.cpd[row] = HUGE_VAL; D.cld[row] = HUGE_VAL; ord_insert(D.ord, D.npts, D.F, row); ++D.npts; } while (0)
-    /* several ranks: the clock and the force_stop flag are decided by all ranks together at the start of every phase (comm.c);
-     * sp is what those two tests look at until the next agreement */
-#define AGREE() do { sp = nla_comm_agree_stop(D.comm, stop, &agreed_view, &agreed_force); \
-        if (!sp) { snprintf(D.err, sizeof D.err, "stop agreement failed: %s", nlopt_amd_comm_error(D.comm)); DEVFAIL(); } } while (0)
-#define STOPS(fv) do { if (nla_stop_forced(sp)) ret = NLOPT_FORCED_STOP; else if (nla_stop_evals(stop)) ret = NLOPT_MAXEVAL_REACHED; \
-        else if (nla_stop_time(sp)) ret = NLOPT_MAXTIME_REACHED; else if ((fv) < stop->minf_max) ret = NLOPT_MINF_MAX_REACHED; } while (0)
-#define GET_MINF() do { if (D.npts) { best_f = D.F[D.ord[0]]; best_row = D.ord[0]; best_is_lm = 0; } \
-        if (D.nlms && D.LF[D.lord[0]] < best_f) { best_f = D.LF[D.lord[0]]; best_row = D.lord[0]; best_is_lm = 1; } } while (0)
+ * leaves; what the pass wrote is not looked at again.  Allocation first: nothing is enqueued before the scratch is large enough. */
+static int mlsl_enqueue_distances(mlsl_dev *d, size_t old)
+{
+    const int na = d->N, nb = (int) (old + (size_t) d->N);
+    const int per = (na + d->world - 1) / d->world;
+    const int r0 = per * d->rank < na ? per * d->rank : na;
+    const int mine = na - r0 < per ? na - r0 : per;
+    if (need_D(d, (size_t) na * (size_t) nb) || (d->nlms && need_D(d, (size_t) na * d->nlms))) return -1;
+    if (nla_memcpy_h2d(d->d_cpd, d->cpd, sizeof(double) * (size_t) nb, d->st) ||
+        nla_memcpy_h2d(d->d_min, d->minimized, sizeof(int32_t) * (size_t) nb, d->st) ||
+        mlsl_closest_pt_pass(d, d->st, old, r0, mine, d->d_D, d->d_cpd, d->d_min) ||
+        nla_memcpy_d2h(d->cpd, d->d_cpd, sizeof(double) * (size_t) nb, d->st) ||
+        mlsl_closest_lm_pass(d, d->st, old, r0, mine, 0, d->nlms, d->d_D, d->d_tmp, d->cld + old + r0)) MFAIL(d, "distance pass failed");
+    return 0;
+}
 
-    /* f of `cnt` rows on the device: compiled-in objective, or the user's kernel (host objectives are called in the loops below) */
-#define EVAL_ROWS(rows, cnt, dF) (D.ev.kind == NLA_EVAL_USER ? nla_userobj_eval_rows(D.ev.user, n, D.ld, (cnt), (rows), (dF), NULL, D.ev.sign, D.st) \
-                                                              : (nla_k_eval(D.obj, n, D.ld, (rows), (cnt), (dF), D.st) || \
-                                                                 (D.ev.sign < 0 && nla_k_mlsl_negate((dF), (int) (cnt), D.st))))
-    /* the starting guess is the first point (mlsl.c:326-340) */
-    if (host) {
-        D.F[0] = f((unsigned) n, x, NULL, f_data);
-        if (nla_memcpy_h2d(D.d_P, x, sizeof(double) * (size_t) n, D.st) || nla_memcpy_h2d(D.d_F, D.F, sizeof(double), D.st) ||
-            nla_stream_sync(D.st)) { snprintf(D.err, sizeof D.err, "first evaluation failed"); DEVFAIL(); }
-    } else if (nla_memcpy_h2d(D.d_P, x, sizeof(double) * (size_t) n, D.st) || EVAL_ROWS(D.d_P, 1, D.d_F) ||
-        nla_memcpy_d2h(D.F, D.d_F, sizeof(double), D.st) || nla_stream_sync(D.st)) { snprintf(D.err, sizeof D.err, "first evaluation failed"); DEVFAIL(); }
-    ++*stop->nevals_p;
-    NEWPT(0);
-    if (D.F[0] != D.F[0]) D.ord_has_nan = 1;
-    AGREE();
-    STOPS(D.F[0]);
+/* the samples were made beside the last local phase (mlsl_enqueue_ahead): nothing to launch for them.  What is left of the distance
+ * pass: the new rows against the minima found since (this stream's work waits for the rows); then the values and the closest-point
+ * minima are merged by `min` */
+static int mlsl_take_ahead(mlsl_dev *d, size_t old)
+{
+    const size_t l0 = d->ahead_nlms, lc = d->nlms - d->ahead_nlms;
+    size_t j;
+    if (nla_stream_wait_event(d->st, d->ev_ahead)) MFAIL(d, "sampling failed");
+    if (lc && (need_D(d, (size_t) d->N * lc) ||
+               mlsl_closest_lm_pass(d, d->st, old, 0, d->N, l0, lc, d->d_D, d->d_tmp, d->cld + old))) MFAIL(d, "distance pass failed");
+    if (nla_event_sync(d->ev_ahead)) MFAIL(d, "sampling failed");
+    memcpy(d->Fnew, d->Fnew2, sizeof(double) * (size_t) d->N);
+    if (d->stats) ++d->stats->mlsl_sampled_ahead;
+    for (j = 0; j < old + (size_t) d->N; ++j) if (d->h_cpd2[j] < d->cpd[j]) d->cpd[j] = d->h_cpd2[j];
+    return 0;
+}
 
-    while (ret == NLOPT_SUCCESS) {
-        double R, t0 = nla_seconds();
-        size_t old = D.npts, used = 0, idx;
-        int remaining, prefetch_due = 0, ahead_due = 0, dist_enqueued = 0, pairs_enqueued = 0, ahead_hit;
-        mlsl_pairs_job pairs_job;
-        GET_MINF();                                                            /* mlsl.c:347 */
-        AGREE();
-        if (opt && opt->progress) { opt->progress(opt->progress_data, st ? (long) st->generations : 0, (long) *stop->nevals_p); t0 = nla_seconds(); }
+/* the host's walk over the N values in the reference's order (mlsl.c:360-368): a host objective is called here; counts, trace, the stop
+ * tests after every sample; then the ordered insertion of the rows walked and the stream accounting.  Returns the samples used. */
+static size_t mlsl_walk_samples(mlsl_dev *d, size_t old)
+{
+    double *Fnew = d->Fnew;
+    size_t used = 0;
+    int i;
+    for (i = 0; i < d->N && d->ret == NLOPT_SUCCESS; ++i) {
+        if (d->host) Fnew[i] = d->f((unsigned) d->n, d->h_rows + (size_t) i * (size_t) d->ld, NULL, d->f_data);   /* mlsl.c:360 */
+        d->F[old + (size_t) i] = Fnew[i];
+        ++*d->stop->nevals_p;
+        if (d->stats) ++d->stats->evals_trial;
+        ++d->npts;                             /* (entries initialised in front of the walk; ord_insert_run follows) */
+        used = (size_t) i + 1;
+        mlsl_trace(d->opt, Fnew[i], old + (size_t) i, 3, 0);
+        d->ret = mlsl_stop_after_sample(d, Fnew[i]);
+    }
+    ord_insert_run(d->ord, old, d->F, old, used, d->ord_has_nan);
+    for (i = 0; i < (int) used && !d->ord_has_nan; ++i) if (d->F[old + (size_t) i] != d->F[old + (size_t) i]) d->ord_has_nan = 1;
+    if (d->d_V) d->sobol_next += (uint32_t) used;
+    else d->words_used += 2ULL * (uint64_t) d->n * (uint64_t) used;
+    return used;
+}
 
-        /* ---- sampling phase (mlsl.c:349-374) ---- */
-        if (grow_pts(&D, old + (size_t) D.N)) DEVFAIL();
-        ahead_hit = D.ahead_valid && D.ahead_old == old && (D.d_V ? D.ahead_sobol == D.sobol_next : D.ahead_words == D.words_used);
-        D.ahead_valid = 0;
-        if (ahead_hit) {
-            /* the samples were made beside the last local phase (mlsl_enqueue_ahead): nothing to launch for them */
-        } else if (D.d_V) {                                                    /* nlopt_sobol_next, mlsl.c:355 */
-            if ((uint64_t) D.sobol_next + (uint64_t) D.N >= 4294967295ULL) { snprintf(D.err, sizeof D.err, "Sobol sequence exhausted (2^32-1 points)"); DEVFAIL(); }
-            if (nla_k_mlsl_sobol_rows(n, D.ld, D.d_lb, D.d_ub, D.d_V, D.sobol_next, D.N, D.d_P + old * (size_t) D.ld, D.st) ||
-                (!host && EVAL_ROWS(D.d_P + old * (size_t) D.ld, D.N, D.d_F + old))) { snprintf(D.err, sizeof D.err, "sampling failed"); DEVFAIL(); }
+static int mlsl_sampling_phase(mlsl_dev *d, double t0)
+{
+    const size_t old = d->npts;
+    size_t used;
+    int i, dist_enqueued = 0, ahead_hit;
+    if (grow_pts(d, old + (size_t) d->N)) return -1;
+    ahead_hit = d->ahead_valid && d->ahead_old == old && (d->d_V ? d->ahead_sobol == d->sobol_next : d->ahead_words == d->words_used);
+    d->ahead_valid = 0;
+    if (!ahead_hit) {
+        if (d->d_V) {
+            if ((uint64_t) d->sobol_next + (uint64_t) d->N >= 4294967295ULL) MFAIL(d, "Sobol sequence exhausted (2^32-1 points)");
         } else {
-            if (D.prefetched_at != D.words_used &&
-                nla_mtstream_fill(D.mts, D.words_used, 2ULL * (uint64_t) n * (uint64_t) D.N, D.d_words)) { snprintf(D.err, sizeof D.err, "MT stream fill failed"); DEVFAIL(); }
-            if (D.rs != D.st && nla_stream_sync(D.rs)) { snprintf(D.err, sizeof D.err, "MT stream fill failed"); DEVFAIL(); }   /* the words are there */
-            if (nla_k_crs_init_rows(D.obj, n, D.ld, D.d_lb, D.d_ub, D.d_words, (int64_t) old, D.N, D.d_P, D.d_F, D.st) ||
-                (D.ev.kind == NLA_EVAL_DEVICE && D.ev.sign < 0 && nla_k_mlsl_negate(D.d_F + old, D.N, D.st)) ||
-                (D.ev.kind == NLA_EVAL_USER && EVAL_ROWS(D.d_P + old * (size_t) D.ld, D.N, D.d_F + old))) { snprintf(D.err, sizeof D.err, "sampling failed"); DEVFAIL(); }
+            if (d->prefetched_at != d->words_used &&
+                nla_mtstream_fill(d->mts, d->words_used, 2ULL * (uint64_t) d->n * (uint64_t) d->N, d->d_words)) MFAIL(d, "MT stream fill failed");
+            if (d->rs != d->st && nla_stream_sync(d->rs)) MFAIL(d, "MT stream fill failed");   /* the words are there */
         }
-        /* the new rows' closest-distance entries and flags start as "none yet" (what NEWPT does per point; here for all N at once so
-         * that the distance pass can be enqueued before the host looks at a single value) */
-        for (i = 0; i < D.N; ++i) { D.minimized[old + (size_t) i] = 0; D.cpd[old + (size_t) i] = HUGE_VAL; D.cld[old + (size_t) i] = HUGE_VAL; }
-        dist_enqueued = 0;
-        if (ahead_hit) {
-            /* what is left of the distance pass: the new rows against the minima found since (this stream's work waits for the rows) */
-            const size_t l0 = D.ahead_nlms, lc = D.nlms - D.ahead_nlms;
-            size_t j;
-            if (nla_stream_wait_event(D.st, D.ev_ahead)) { snprintf(D.err, sizeof D.err, "sampling failed"); DEVFAIL(); }
-            if (lc && (need_D(&D, (size_t) D.N * lc) ||
-                       nla_k_mlsl_dist2(n, D.ld, D.d_P + old * (size_t) D.ld, D.N, D.d_LM + l0 * (size_t) D.ld, (int) lc, D.d_D, D.st) ||
-                       nla_k_mlsl_rowmin(D.d_D, (int) lc, D.N, (int) lc, D.d_F + old, D.d_LF + l0, NULL, D.d_tmp, D.st) ||
-                       nla_memcpy_d2h(D.cld + old, D.d_tmp, sizeof(double) * (size_t) D.N, D.st))) { snprintf(D.err, sizeof D.err, "distance pass failed"); DEVFAIL(); }
-            if (nla_event_sync(D.ev_ahead)) { snprintf(D.err, sizeof D.err, "sampling failed"); DEVFAIL(); }
-            memcpy(Fnew, D.Fnew2, sizeof(double) * (size_t) D.N);
-            if (st) ++st->mlsl_sampled_ahead;
-            for (j = 0; j < old + (size_t) D.N; ++j) if (D.h_cpd2[j] < D.cpd[j]) D.cpd[j] = D.h_cpd2[j];
+        if (mlsl_sample_rows(d, d->st, old, !d->host)) MFAIL(d, "sampling failed");
+    }
+    /* the new rows' closest-distance entries and flags start as "none yet" (what pts_insert does per point; here for all N at once so
+     * that the distance pass can be enqueued before the host looks at a single value) */
+    for (i = 0; i < d->N; ++i) { d->minimized[old + (size_t) i] = 0; d->cpd[old + (size_t) i] = HUGE_VAL; d->cld[old + (size_t) i] = HUGE_VAL; }
+    if (ahead_hit) {
+        if (mlsl_take_ahead(d, old)) return -1;
+        dist_enqueued = 1;                                                     /* (everything is enqueued or done) */
+    } else {
+        if (d->host ? nla_memcpy_d2h(d->h_rows, d->d_P + old * (size_t) d->ld, sizeof(double) * (size_t) d->N * (size_t) d->ld, d->st)
+                    : nla_memcpy_d2h(d->Fnew, d->d_F + old, sizeof(double) * (size_t) d->N, d->st)) MFAIL(d, "sampling failed");
+        if (!d->host && d->world == 1) {
+            /* wait for the values only (an event behind their copy, recorded BEFORE the distance pass goes out and synchronised
+             * after it), with the distance pass already behind them on the stream */
+            if (nla_event_record(d->ev_samples, d->st)) MFAIL(d, "sampling failed");
+            if (mlsl_enqueue_distances(d, old)) return -1;
             dist_enqueued = 1;
-        } else
-        if (host ? nla_memcpy_d2h(D.h_rows, D.d_P + old * (size_t) D.ld, sizeof(double) * (size_t) D.N * (size_t) D.ld, D.st)
-                 : nla_memcpy_d2h(Fnew, D.d_F + old, sizeof(double) * (size_t) D.N, D.st)) { snprintf(D.err, sizeof D.err, "sampling failed"); DEVFAIL(); }
-        if (ahead_hit) {
-            /* (everything is enqueued or done) */
-        } else if (!host && D.world == 1) {
-            /* wait for the values only (an event behind their copy), with the distance pass already behind them on the stream */
-            if (nla_event_record(D.ev_samples, D.st)) { snprintf(D.err, sizeof D.err, "sampling failed"); DEVFAIL(); }
-            ENQUEUE_DISTANCES();
-            if (nla_event_sync(D.ev_samples)) { snprintf(D.err, sizeof D.err, "sampling failed"); DEVFAIL(); }
-        } else if (nla_stream_sync(D.st)) { snprintf(D.err, sizeof D.err, "sampling failed"); DEVFAIL(); }
-        for (i = 0; i < D.N && ret == NLOPT_SUCCESS; ++i) {
-            if (host) Fnew[i] = f((unsigned) n, D.h_rows + (size_t) i * (size_t) D.ld, NULL, f_data);   /* mlsl.c:360 */
-            D.F[old + (size_t) i] = Fnew[i];
-            ++*stop->nevals_p;
-            if (st) ++st->evals_trial;
-            NEWPT_UNORDERED(old + (size_t) i);
-            used = (size_t) i + 1;
-            if (opt && opt->trace) {
-                if (opt->trace_len < opt->trace_cap) { nlopt_amd_trace_rec *tr = opt->trace + opt->trace_len; tr->f = Fnew[i]; tr->row = (int64_t) (old + (size_t) i); tr->kind = 3; tr->accepted = 0; }
-                ++opt->trace_len;
-            }
-            STOPS(Fnew[i]);
-        }
-        {
-            int any_nan = D.ord_has_nan;
-            ord_insert_run(D.ord, old, D.F, old, used, any_nan);
-            for (i = 0; i < (int) used && !D.ord_has_nan; ++i) if (D.F[old + (size_t) i] != D.F[old + (size_t) i]) D.ord_has_nan = 1;
-        }
-        if (D.d_V) D.sobol_next += (uint32_t) used;
-        else D.words_used += 2ULL * (uint64_t) n * (uint64_t) used;
-        if (host && (nla_memcpy_h2d(D.d_F + old, Fnew, sizeof(double) * used, D.st) || nla_stream_sync(D.st))) { snprintf(D.err, sizeof D.err, "sampling failed"); DEVFAIL(); }
-        if (ret != NLOPT_SUCCESS) break;
-        /* the sampling kernel has read the words (synchronised above): the next iteration's can be generated.  NOT here (round 5,
-         * profiles/r05_mlsl_timeline.txt): enqueued now, the jump-ahead kernel — 33 k workgroups, 0.55 ms, once or twice per iteration —
-         * and the generator had the device to themselves and the distance pass queued up behind them, 0.9-1.8 ms of every iteration.
-         * They go out right in front of the local searches' launch instead (PREFETCH_NOW below), on a background-priority stream: the
-         * searches' 300 workgroups leave most of every compute unit free for 6 ms */
-        prefetch_due = D.prefetch && !D.d_V;
-        ahead_due = D.ahead;
-        if (!dist_enqueued) ENQUEUE_DISTANCES();
-        {
-            const int na = D.N;
-            if (nla_stream_sync(D.st)) { snprintf(D.err, sizeof D.err, "distance pass failed"); DEVFAIL(); }
-            if (ahead_hit && D.ahead_nlms)                                      /* closest_lm_d: the minima known when the rows were made | those found since */
-                for (i = 0; i < na; ++i) if (D.h_cld2[i] < D.cld[old + (size_t) i]) D.cld[old + (size_t) i] = D.h_cld2[i];
-            if (D.world > 1 && (min_over_ranks(&D, D.cpd, D.npts) || (D.nlms && min_over_ranks(&D, D.cld + old, (size_t) na)))) {
-                snprintf(D.err, sizeof D.err, "all-gather of the distance minima failed: %s", nlopt_amd_comm_error(D.comm)); DEVFAIL();
-            }
-        }
-        if (st) st->t_eval_s += nla_seconds() - t0;
+            if (nla_event_sync(d->ev_samples)) MFAIL(d, "sampling failed");
+        } else if (nla_stream_sync(d->st)) MFAIL(d, "sampling failed");
+    }
+    used = mlsl_walk_samples(d, old);
+    if (d->host && (nla_memcpy_h2d(d->d_F + old, d->Fnew, sizeof(double) * used, d->st) || nla_stream_sync(d->st))) MFAIL(d, "sampling failed");
+    if (d->ret != NLOPT_SUCCESS) return 0;
+    /* the sampling kernel has read the words (synchronised above): the next iteration's can be generated.  NOT here (round 5,
+     * profiles/r05_mlsl_timeline.txt): enqueued now, the jump-ahead kernel — 33 k workgroups, 0.55 ms, once or twice per iteration —
+     * and the generator had the device to themselves and the distance pass queued up behind them, 0.9-1.8 ms of every iteration.
+     * They go out right in front of the local searches' launch instead (mlsl_prefetch_now), on a background-priority stream: the
+     * searches' 300 workgroups leave most of every compute unit free for 6 ms */
+    d->prefetch_due = d->prefetch && !d->d_V;
+    d->ahead_due = d->ahead;
+    if (!dist_enqueued && mlsl_enqueue_distances(d, old)) return -1;
+    if (nla_stream_sync(d->st)) MFAIL(d, "distance pass failed");
+    if (ahead_hit && d->ahead_nlms)                                            /* closest_lm_d: the minima known when the rows were made | those found since */
+        for (i = 0; i < d->N; ++i) if (d->h_cld2[i] < d->cld[old + (size_t) i]) d->cld[old + (size_t) i] = d->h_cld2[i];
+    if (d->world > 1 && (min_over_ranks(d, d->cpd, d->npts) || (d->nlms && min_over_ranks(d, d->cld + old, (size_t) d->N))))
+        MFAIL(d, "all-gather of the distance minima failed: %s", nlopt_amd_comm_error(d->comm));
+    if (d->stats) d->stats->t_eval_s += nla_seconds() - t0;
+    return 0;
+}
 
-        /* ---- local phase (mlsl.c:377-428) ---- */
-        t0 = nla_seconds();
-        R = R_prefactor * pow(log((double) D.npts) / D.npts, 1.0 / n);
-        idx = 0;
-        remaining = (int) (ceil(MLSL_GAMMA * D.npts) + 0.5);
-        while (idx < D.npts && remaining > 0 && ret == NLOPT_SUCCESS) {
-            int nb = 0, c, per, mine = 0, nacc = 0;
-            size_t scan = idx, nlms0 = 0;
-            int rem = remaining, eff;
-            long limited;
-            /* the next candidates that are potential minimisers right now (is_potential_minimizer, :196-221) */
-            while (scan < D.npts && rem > 0 && nb < bmax) {
-                const size_t r = D.ord[scan];
-                ++scan; --rem;
-                if (D.minimized[r] || D.cpd[r] <= R * R || D.cld[r] <= (dlm * R) * (dlm * R)) continue;
-                cand[nb++] = scan - 1;
-            }
-            if (nb == 0) { idx = scan; remaining = rem; break; }
-            AGREE();
-            /* candidate c is minimised by rank c mod world in its slot c / world; gathered row of c: GI(c) */
-            per = (nb + D.world - 1) / D.world;
-#define GI(c) ((size_t) ((c) % D.world) * (size_t) per + (size_t) ((c) / D.world))
-            /* start points of this rank's share into the batch (one gather launch), and the bound test of every candidate
-             * (is_potential_minimizer, mlsl.c:211-218) on the device: only the flags come back */
-            for (c = 0; c < nb; ++c) D.h_idx[c] = (int64_t) D.ord[cand[c]];
-            for (c = D.rank; c < nb; c += D.world, ++mine) D.h_idx[bmax + mine] = (int64_t) D.ord[cand[c]];
-            if (nla_memcpy_h2d(D.d_idx, D.h_idx, sizeof(int64_t) * (size_t) (bmax + mine), D.st) ||
-                nla_k_mlsl_gather_rows(n, D.ld, D.d_P, D.d_idx + bmax, mine, use_cobyla ? D.d_LX : nla_local_ctx_X(D.lb), D.st) ||
-                nla_k_mlsl_near_bound(n, D.ld, D.d_P, D.d_idx, nb, D.d_lb, D.d_ub, dbound * R, D.d_flags, D.st) ||
-                nla_memcpy_d2h(D.h_flags, D.d_flags, sizeof(int32_t) * (size_t) nb, D.st)) { snprintf(D.err, sizeof D.err, "gather failed"); DEVFAIL(); }
-            /* local searches of this rank's share, all-gather of the minimisers, then their distances to every point */
-            if (host && D.world == 1) {
-                /* a host objective sees its calls: the tests the reference makes in front of a search (mlsl.c:390-399) are made
-                 * here, before the search's first callback, not at commit time */
-                if (nla_stream_sync(D.st)) { snprintf(D.err, sizeof D.err, "gather failed"); DEVFAIL(); }
-                if (D.h_flags[0]) mine = 0;                                         /* too close to a bound: not started */
-                else if (nla_stop_forced(stop)) ret = NLOPT_FORCED_STOP;
-                else if (nla_stop_evals(stop)) ret = NLOPT_MAXEVAL_REACHED;
-                else if (stop->maxtime > 0 && nla_seconds() - stop->start >= stop->maxtime) ret = NLOPT_MAXTIME_REACHED;
-                if (ret != NLOPT_SUCCESS) break;
-            }
-            limited = (long) stop->maxeval - (long) *stop->nevals_p;             /* nlopt_optimize_limited, optimize.c:1097-1100 */
-            eff = loc_maxeval;
-            if (loc_maxeval <= 0 || (limited > 0 && limited < loc_maxeval)) eff = (int) limited;
-            prm.maxeval = eff;
-            if (use_cobyla) {
-                memset(&res[0], 0, sizeof res[0]);
-                if (mine > 0) {                                                     /* mlsl.c:400-407 */
-                    const double t = nla_seconds();
-                    double lf = HUGE_VAL;
-                    nlopt_result lret;
-                    if (nla_memcpy_d2h(cob_x, D.d_LX, sizeof(double) * (size_t) n, D.st) || nla_stream_sync(D.st)) { snprintf(D.err, sizeof D.err, "gather failed"); DEVFAIL(); }
-                    lret = nla_optimize_limited(local_opt, cob_x, &lf, stop->maxeval - *stop->nevals_p, stop->maxtime - (t - stop->start));
-                    if (nla_memcpy_h2d(D.d_LX, cob_x, sizeof(double) * (size_t) n, D.st) || nla_stream_sync(D.st)) { snprintf(D.err, sizeof D.err, "minimum store failed"); DEVFAIL(); }
-                    res[0].ret = (int) lret; res[0].f = lf;
-                    res[0].nevals = 0; res[0].iterm = 0;                            /* the calls were counted one by one (mlsl_counted_f) */
-                }
-            } else {
-            pairs_enqueued = 0;
-            if (!host && D.world == 1 && mine > 0) {
-                /* one rank, device objective: the minimisers' distances go out right behind the searches' kernel (they need nothing the
-                 * host decides), instead of after the host has woken up, copied the results and come back: 0.2 ms per iteration */
-                pairs_job.d = &D; pairs_job.n = n; pairs_job.nb = nb; pairs_job.na = (size_t) per; pairs_job.ctx_X = nla_local_ctx_X(D.lb);
-                pairs_job.lx_bytes = sizeof(double) * (size_t) per * (size_t) D.ld;
-                if (need_D(&D, (size_t) per * D.npts)) DEVFAIL();
-                for (c = 0; c < nb; ++c) D.h_gi[c] = (int64_t) GI(c);
-                nla_local_ctx_after_launch(D.lb, mlsl_enqueue_pairs, &pairs_job);
-                pairs_enqueued = 1;
-            }
-            /* (in front of the launch, behind everything that may allocate: freeing device memory waits for every stream, the gate included) */
-            D.gate_need = 0;
-            if (D.ahead && mine > 0 && (D.gate_counter = nla_local_ctx_finished_counter(D.lb, &D.gate_from))) D.gate_need = (mine * NLA_MLSL_GATE_PCT + 99) / 100;
-            PREFETCH_NOW();
-            D.gate_need = 0;
-            if (mine > 0 && nla_local_ctx_run(D.lb, mine, &prm, res_mine, &lstop, NULL)) { snprintf(D.err, sizeof D.err, "local-search batch failed"); DEVFAIL(); }
-            if ((!pairs_enqueued && nla_comm_allgather_dev(D.comm, nla_local_ctx_X(D.lb), D.d_LX, sizeof(double) * (size_t) per * (size_t) D.ld, D.st)) ||
-                nla_comm_allgather_host(D.comm, res_mine, res, sizeof *res * (size_t) per, D.st)) {
-                snprintf(D.err, sizeof D.err, "all-gather of the local minima failed: %s", nlopt_amd_comm_error(D.comm)); DEVFAIL();
-            }
-            }
-            {
-                /* the distances of the batch's minimisers to every point stay on the device (na x npts: 12 MB at config 4); the commit walk
-                 * below only needs those to the batch's OWN start points (whether an earlier commit of the batch disqualified a later
-                 * candidate, mlsl.c:180-194 seen from :196-221) — nb x nb values — and pts_update_newlm for all the other points is an
-                 * order-independent min that one launch computes once the accepted set is known */
-                const size_t na = (size_t) per * (size_t) D.world;
-                if (need_D(&D, na * D.npts)) DEVFAIL();
-                if (!pairs_enqueued) {
-                    for (c = 0; c < nb; ++c) D.h_gi[c] = (int64_t) GI(c);
-                    pairs_job.d = &D; pairs_job.n = n; pairs_job.nb = nb; pairs_job.na = na; pairs_job.ctx_X = NULL; pairs_job.lx_bytes = 0;
-                    if (mlsl_enqueue_pairs(&pairs_job)) { snprintf(D.err, sizeof D.err, "distance pass failed"); DEVFAIL(); }
-                }
-                if (nla_stream_sync(D.st)) { snprintf(D.err, sizeof D.err, "distance pass failed"); DEVFAIL(); }
-                for (c = 0; c < (int) na; ++c) D.h_lfall[c] = HUGE_VAL;
-                for (c = 0; c < nb; ++c) D.lf_cand[c] = HUGE_VAL;
-            }
-            if (grow_lms(&D, D.nlms + (size_t) nb)) DEVFAIL();
-            nacc = 0; nlms0 = D.nlms;
-            /* commit in walk order */
-            for (c = 0; c < nb && ret == NLOPT_SUCCESS; ++c) {
-                const size_t r = D.ord[cand[c]];
-                double lf, cl = D.cld[r];
-                int calls, pot, cp;
-                const size_t g = GI(c);
-                /* closest_lm_d of this start as the serial order would see it now: the minima committed earlier in this batch count
-                 * (pts_update_newlm, mlsl.c:180-194: those with smaller f than the point's, if closer) */
-                /* (h_S[c][cp] = distance of start c to minimiser cp: transposed on the device.  nb^2 / 2 questions per batch — 46 k at config 4:
-                 * with the gathered-row index GI(cp), a division and a remainder, inside the loop they were the better part of the 0.6 ms the
-                 * device waited for this walk) */
-                {
-                    const double Fr = D.F[r], *Sc = D.h_S + (size_t) c * (size_t) nb, *lfc = D.lf_cand;
-                    for (cp = 0; cp < c; ++cp)
-                        if (lfc[cp] < Fr && Sc[cp] < cl) cl = Sc[cp];
-                }
-                pot = !(cl <= (dlm * R) * (dlm * R));
-                /* nodes between the previous candidate and this one were visited and skipped */
-                remaining -= (int) (cand[c] + 1 - idx);
-                idx = cand[c] + 1;
-                if (pot && D.h_flags[c]) pot = 0;                               /* too close to a bound (mlsl.c:211-218) */
-                if (!pot) continue;
-                if (!(host && D.world == 1)) {
-                    if (nla_stop_forced(sp)) { ret = NLOPT_FORCED_STOP; break; }
-                    if (nla_stop_evals(stop)) { ret = NLOPT_MAXEVAL_REACHED; break; }
-                    if (nla_stop_time(sp)) { ret = NLOPT_MAXTIME_REACHED; break; }
-                }
-                /* did this search run under the evaluation limit it would have had in the serial order? */
-                limited = (long) stop->maxeval - (long) *stop->nevals_p;
-                eff = loc_maxeval;
-                if (loc_maxeval <= 0 || (limited > 0 && limited < loc_maxeval)) eff = (int) limited;
-                if (eff > 0 && eff != prm.maxeval && res[g].nevals >= eff) {
-                    /* the limit binds differently than assumed: redo this one search alone with the exact limit
-                     * (every rank does, identically; the gathered rows of the other candidates are untouched) */
-                    nla_lbfgs_params p1 = prm;
-                    nla_lbfgs_result r1;
-                    p1.maxeval = eff;
-                    if (nla_memcpy_d2d(nla_local_ctx_X(D.lb), D.d_P + r * (size_t) D.ld, sizeof(double) * (size_t) n, D.st) ||
-                        nla_local_ctx_run(D.lb, 1, &p1, &r1, &lstop, NULL) ||
-                        nla_memcpy_d2d(D.d_LX + g * (size_t) D.ld, nla_local_ctx_X(D.lb), sizeof(double) * (size_t) n, D.st) ||
-                        nla_k_mlsl_dist2(n, D.ld, D.d_LX + g * (size_t) D.ld, 1, D.d_P, (int) D.npts, D.d_D + g * D.npts, D.st) ||
-                        nla_memcpy_d2h(D.h_D, D.d_D + g * D.npts, sizeof(double) * D.npts, D.st) || nla_stream_sync(D.st)) { snprintf(D.err, sizeof D.err, "local-search rerun failed"); DEVFAIL(); }
-                    for (cp = 0; cp < nb; ++cp) D.h_S[(size_t) cp * (size_t) nb + (size_t) c] = D.h_D[D.ord[cand[cp]]];     /* this minimiser moved: its distances to the batch's start points */
-                    res[g] = r1;
-                }
-                calls = use_mma ? res[g].iterm : res[g].nevals;                /* objective calls the search made (MMA: iterm) */
-                *stop->nevals_p += calls;                                       /* fcount, mlsl.c:246-251 */
-                if (st) { st->evals_mutation += (uint64_t) calls; ++st->accepted; }
-                D.minimized[r] = 1;
-                if (opt && opt->trace) {
-                    if (opt->trace_len < opt->trace_cap) { nlopt_amd_trace_rec *tr = opt->trace + opt->trace_len; tr->f = res[g].f; tr->row = (int64_t) r; tr->kind = 4; tr->accepted = calls; }
-                    ++opt->trace_len;
-                }
-                if (res[g].ret < 0) { ret = (nlopt_result) res[g].ret; goto done_noget; }
-                lf = res[g].f;
-                /* the minimum joins the device-side set; stream-ordered, no synchronisation per minimum (room for the whole
-                 * batch was made before the walk; res[] stays valid until the batch's closing synchronisation) */
-                D.h_idx[bmax + BATCH_MAX + nacc] = (int64_t) g;
-                D.h_lf[nacc] = lf;
-                D.h_lfall[g] = lf;
-                D.lf_cand[c] = lf;
-                ++nacc;
-                D.LF[D.nlms] = lf;
-                ord_insert(D.lord, D.nlms, D.LF, D.nlms);
-                ++D.nlms;
-                if (nla_stop_forced(sp)) ret = NLOPT_FORCED_STOP;
-                else if (lf < stop->minf_max) ret = NLOPT_MINF_MAX_REACHED;
-                else if (nla_stop_evals(stop)) ret = NLOPT_MAXEVAL_REACHED;
-                else if (nla_stop_time(sp)) ret = NLOPT_MAXTIME_REACHED;
-                /* (pts_update_newlm for this minimum: with the batch's other accepted minima, in one launch below.  A minimum whose commit
-                 * ends the run updated nothing in the reference either — the stop tests come first, mlsl.c:417-425 — so it is left out.) */
-                if (ret != NLOPT_SUCCESS) { D.h_lfall[g] = HUGE_VAL; D.lf_cand[c] = HUGE_VAL; }
-            }
-            /* pts_update_newlm (mlsl.c:180-194) for every accepted minimum of the batch at once: closest_lm_d[k] = min over the accepted
-             * minima with smaller f than point k of their distance to k — a min, so the order of the commits does not matter.  (The
-             * reference skips minimised points; their closest_lm_d is never read again, mlsl.c:200, so no flag is consulted here.) */
-            if (nacc > 0 && (nla_memcpy_h2d(D.d_lfall, D.h_lfall, sizeof(double) * (size_t) per * (size_t) D.world, D.st) ||
-                             nla_memcpy_h2d(D.d_cpd, D.cld, sizeof(double) * D.npts, D.st) ||
-                             nla_k_mlsl_colmin(D.d_D, (int) D.npts, per * D.world, (int) D.npts, D.d_lfall, D.d_F, NULL, D.d_cpd, D.st) ||
-                             nla_memcpy_d2h(D.cld, D.d_cpd, sizeof(double) * D.npts, D.st))) { snprintf(D.err, sizeof D.err, "closest-minimum update failed"); DEVFAIL(); }
-            /* the batch's accepted minima join the device-side set in acceptance order: one gather launch */
-            if (nacc > 0 && (nla_memcpy_h2d(D.d_idx + bmax + BATCH_MAX, D.h_idx + bmax + BATCH_MAX, sizeof(int64_t) * (size_t) nacc, D.st) ||
-                             nla_k_mlsl_gather_rows(n, D.ld, D.d_LX, D.d_idx + bmax + BATCH_MAX, nacc, D.d_LM + nlms0 * (size_t) D.ld, D.st) ||
-                             nla_memcpy_h2d(D.d_LF + nlms0, D.h_lf, sizeof(double) * (size_t) nacc, D.st))) { snprintf(D.err, sizeof D.err, "minimum store failed"); DEVFAIL(); }
-            if (nla_stream_sync(D.st)) { snprintf(D.err, sizeof D.err, "minimum store failed"); DEVFAIL(); }
-            if (ret == NLOPT_SUCCESS && c == nb) {
-                /* nodes scanned after the last candidate of the batch (none qualified) are visited too */
-                remaining -= (int) (scan - idx);
-                idx = scan;
-            }
-        }
-        PREFETCH_NOW();                                                        /* (an iteration without a local search) */
-        if (st) { st->t_evolve_s += nla_seconds() - t0; ++st->generations; }
+/* ---- local phase (mlsl.c:377-428) ---- */
+
+/* the walk of one iteration over the best ceil(gamma |pts|) points in `ord`, a batch of candidates at a time */
+typedef struct {
+    double R;                       /* the critical distance of this iteration (mlsl.c:377-379) */
+    size_t idx; int remaining;      /* the walk: next position in ord, nodes left to visit */
+    size_t scan; int rem;           /* the same behind the last node scanned for the current batch */
+    int nb, per, mine;              /* the batch: candidates, slots per rank (gathered rows: per x world), searches of this rank */
+    int pairs_enqueued;             /* the minimisers' distances went out behind the searches' kernel */
+    int nacc; size_t nlms0;         /* minima the commit walk accepted, and where in the minimum set they start */
+} mlsl_walk;
+
+/* the next candidates that are potential minimisers right now (is_potential_minimizer, mlsl.c:196-221; the bound test follows on
+ * the device) */
+static void mlsl_select_candidates(mlsl_dev *d, mlsl_walk *w)
+{
+    const double R = w->R;
+    w->nb = 0; w->scan = w->idx; w->rem = w->remaining;
+    while (w->scan < d->npts && w->rem > 0 && w->nb < d->bmax) {
+        const size_t r = d->ord[w->scan];
+        ++w->scan; --w->rem;
+        if (d->minimized[r] || d->cpd[r] <= R * R || d->cld[r] <= (dlm * R) * (dlm * R)) continue;
+        d->cand[w->nb++] = w->scan - 1;
     }
-    GET_MINF();                                                                /* mlsl.c:431 */
-done_noget:
-    if (ret != NLOPT_FAILURE || best_f < HUGE_VAL) {
-        const double *src = best_is_lm ? D.d_LM + best_row * (size_t) D.ld : D.d_P + best_row * (size_t) D.ld;
-        if (best_f < HUGE_VAL) {
-            *minf = best_f;
-            if (nla_memcpy_d2h(x, src, sizeof(double) * (size_t) n, D.st) || nla_stream_sync(D.st)) { nla_stop_msg(stop, "device engine: result read-back failed"); ret = NLOPT_FAILURE; }
+}
+
+/* the host search of the batch's one candidate (mlsl.c:400-407): through the library's own nlopt_optimize, its calls counted one by one */
+static int mlsl_host_search(mlsl_dev *d, int mine)
+{
+    nla_lbfgs_result *res = d->res;
+    const nla_stopping *stop = d->stop;
+    const size_t xbytes = sizeof(double) * (size_t) d->n;
+    memset(&res[0], 0, sizeof res[0]);
+    if (mine > 0) {
+        const double t = nla_seconds();
+        double lf = HUGE_VAL;
+        nlopt_result lret;
+        if (nla_memcpy_d2h(d->cob_x, d->d_LX, xbytes, d->st) || nla_stream_sync(d->st)) MFAIL(d, "gather failed");
+        lret = nla_optimize_limited(d->local_opt, d->cob_x, &lf, stop->maxeval - *stop->nevals_p, stop->maxtime - (t - stop->start));
+        if (nla_memcpy_h2d(d->d_LX, d->cob_x, xbytes, d->st) || nla_stream_sync(d->st)) MFAIL(d, "minimum store failed");
+        res[0].ret = (int) lret; res[0].f = lf;
+        res[0].nevals = 0; res[0].iterm = 0;                                   /* the calls were counted one by one (mlsl_counted_f) */
+    }
+    return 0;
+}
+
+/* the batched searches of this rank's share on the device, and the all-gather of the minimisers and their results */
+static int mlsl_device_searches(mlsl_dev *d, mlsl_walk *w)
+{
+    const int nb = w->nb, per = w->per, mine = w->mine;
+    mlsl_pairs_job job;
+    int c;
+    if (!d->host && d->world == 1 && mine > 0) {
+        /* one rank, device objective: the minimisers' distances go out right behind the searches' kernel (they need nothing the
+         * host decides), instead of after the host has woken up, copied the results and come back: 0.2 ms per iteration.
+         * (Allocation first: need_D in front of nla_local_ctx_after_launch) */
+        job.d = d; job.nb = nb; job.na = (size_t) per; job.ctx_X = nla_local_ctx_X(d->lb);
+        job.lx_bytes = sizeof(double) * (size_t) per * (size_t) d->ld;
+        if (need_D(d, (size_t) per * d->npts)) return -1;
+        for (c = 0; c < nb; ++c) d->h_gi[c] = (int64_t) mlsl_gi(c, d->world, per);
+        nla_local_ctx_after_launch(d->lb, mlsl_enqueue_pairs, &job);
+        w->pairs_enqueued = 1;
+    }
+    /* the prefetch and the sampling phase ahead go out directly in front of the launch, behind everything that may allocate (freeing
+     * device memory waits for every stream, the gate included); gate_need is non-zero only around this call */
+    d->gate_need = 0;
+    if (d->ahead && mine > 0 && (d->gate_counter = nla_local_ctx_finished_counter(d->lb, &d->gate_from))) d->gate_need = (mine * NLA_MLSL_GATE_PCT + 99) / 100;
+    c = mlsl_prefetch_now(d);
+    d->gate_need = 0;
+    if (c) return -1;
+    if (mine > 0 && nla_local_ctx_run(d->lb, mine, &d->prm, d->res_mine, &d->lstop, NULL)) MFAIL(d, "local-search batch failed");
+    if ((!w->pairs_enqueued && nla_comm_allgather_dev(d->comm, nla_local_ctx_X(d->lb), d->d_LX, sizeof(double) * (size_t) per * (size_t) d->ld, d->st)) ||
+        nla_comm_allgather_host(d->comm, d->res_mine, d->res, sizeof *d->res * (size_t) per, d->st))
+        MFAIL(d, "all-gather of the local minima failed: %s", nlopt_amd_comm_error(d->comm));
+    return 0;
+}
+
+/* start points of this rank's share into the batch (one gather launch), and the bound test of every candidate (is_potential_minimizer,
+ * mlsl.c:211-218) on the device: only the flags come back; then the local searches of this rank's share, the all-gather of the
+ * minimisers, and their distances to every point.  d->ret != NLOPT_SUCCESS afterwards: the run stopped in front of a host search. */
+static int mlsl_launch_batch(mlsl_dev *d, mlsl_walk *w)
+{
+    const int nb = w->nb, bmax = d->bmax;
+    const int per = w->per = (nb + d->world - 1) / d->world;
+    int c, mine = 0;
+    w->pairs_enqueued = 0;
+    for (c = 0; c < nb; ++c) d->h_idx[c] = (int64_t) d->ord[d->cand[c]];
+    for (c = d->rank; c < nb; c += d->world, ++mine) d->h_idx[bmax + mine] = (int64_t) d->ord[d->cand[c]];
+    if (nla_memcpy_h2d(d->d_idx, d->h_idx, sizeof(int64_t) * (size_t) (bmax + mine), d->st) ||
+        nla_k_mlsl_gather_rows(d->n, d->ld, d->d_P, d->d_idx + bmax, mine, d->local == MLSL_HOST_SEARCH ? d->d_LX : nla_local_ctx_X(d->lb), d->st) ||
+        nla_k_mlsl_near_bound(d->n, d->ld, d->d_P, d->d_idx, nb, d->d_lb, d->d_ub, dbound * w->R, d->d_flags, d->st) ||
+        nla_memcpy_d2h(d->h_flags, d->d_flags, sizeof(int32_t) * (size_t) nb, d->st)) MFAIL(d, "gather failed");
+    if (d->host && d->world == 1) {
+        /* a host objective sees its calls: the tests the reference makes in front of a search (mlsl.c:390-399) are made
+         * here, before the search's first callback, not at commit time */
+        if (nla_stream_sync(d->st)) MFAIL(d, "gather failed");
+        if (d->h_flags[0]) mine = 0;                                           /* too close to a bound: not started */
+        else d->ret = mlsl_stop_before_host_search(d);
+        if (d->ret != NLOPT_SUCCESS) return 0;
+    }
+    w->mine = mine;
+    d->prm.maxeval = mlsl_eval_limit(d);
+    if (d->local == MLSL_HOST_SEARCH ? mlsl_host_search(d, mine) : mlsl_device_searches(d, w)) return -1;
+    {
+        /* the distances of the batch's minimisers to every point stay on the device (na x npts: 12 MB at config 4); the commit walk
+         * only needs those to the batch's OWN start points (whether an earlier commit of the batch disqualified a later
+         * candidate, mlsl.c:180-194 seen from :196-221) — nb x nb values — and pts_update_newlm for all the other points is an
+         * order-independent min that one launch computes once the accepted set is known */
+        const size_t na = (size_t) per * (size_t) d->world;
+        if (need_D(d, na * d->npts)) return -1;
+        if (!w->pairs_enqueued) {
+            mlsl_pairs_job job;
+            for (c = 0; c < nb; ++c) d->h_gi[c] = (int64_t) mlsl_gi(c, d->world, per);
+            job.d = d; job.nb = nb; job.na = na; job.ctx_X = NULL; job.lx_bytes = 0;
+            if (mlsl_enqueue_pairs(&job)) MFAIL(d, "distance pass failed");
+        }
+        if (nla_stream_sync(d->st)) MFAIL(d, "distance pass failed");
+        for (c = 0; c < (int) na; ++c) d->h_lfall[c] = HUGE_VAL;
+        for (c = 0; c < nb; ++c) d->lf_cand[c] = HUGE_VAL;
+    }
+    return 0;
+}
+
+/* the limit binds differently than assumed: redo the one search of candidate c (start row r, gathered row g) alone with the exact
+ * limit (every rank does, identically; the gathered rows of the other candidates are untouched) */
+static int mlsl_rerun_search(mlsl_dev *d, const mlsl_walk *w, int c, size_t r, size_t g, int eff)
+{
+    const size_t xbytes = sizeof(double) * (size_t) d->n;
+    const int nb = w->nb;
+    nla_lbfgs_params p1 = d->prm;
+    nla_lbfgs_result r1;
+    int cp;
+    p1.maxeval = eff;
+    if (nla_memcpy_d2d(nla_local_ctx_X(d->lb), d->d_P + r * (size_t) d->ld, xbytes, d->st) ||
+        nla_local_ctx_run(d->lb, 1, &p1, &r1, &d->lstop, NULL) ||
+        nla_memcpy_d2d(d->d_LX + g * (size_t) d->ld, nla_local_ctx_X(d->lb), xbytes, d->st) ||
+        nla_k_mlsl_dist2(d->n, d->ld, d->d_LX + g * (size_t) d->ld, 1, d->d_P, (int) d->npts, d->d_D + g * d->npts, d->st) ||
+        nla_memcpy_d2h(d->h_D, d->d_D + g * d->npts, sizeof(double) * d->npts, d->st) || nla_stream_sync(d->st)) MFAIL(d, "local-search rerun failed");
+    for (cp = 0; cp < nb; ++cp) d->h_S[(size_t) cp * (size_t) nb + (size_t) c] = d->h_D[d->ord[d->cand[cp]]];     /* this minimiser moved: its distances to the batch's start points */
+    d->res[g] = r1;
+    return 0;
+}
+
+/* commit the batch in walk order (mlsl.c:385-425 for each candidate, as the serial order would see it) */
+static int mlsl_commit_batch(mlsl_dev *d, mlsl_walk *w)
+{
+    nlopt_amd_stats *st = d->stats;
+    nla_stopping *stop = d->stop;
+    nla_lbfgs_result *res = d->res;
+    const size_t *cand = d->cand;
+    const double R = w->R;
+    const int nb = w->nb, bmax = d->bmax, use_mma = d->local == MLSL_MMA;
+    const int tests_at_commit = !(d->host && d->world == 1);                   /* (else: made in front of the search, mlsl_launch_batch) */
+    int c;
+    if (grow_lms(d, d->nlms + (size_t) nb)) return -1;
+    w->nacc = 0; w->nlms0 = d->nlms;
+    for (c = 0; c < nb && d->ret == NLOPT_SUCCESS; ++c) {
+        const size_t r = d->ord[cand[c]];
+        double lf, cl = d->cld[r];
+        int calls, pot, cp, eff;
+        const size_t g = mlsl_gi(c, d->world, w->per);
+        /* closest_lm_d of this start as the serial order would see it now: the minima committed earlier in this batch count
+         * (pts_update_newlm, mlsl.c:180-194: those with smaller f than the point's, if closer) */
+        /* (h_S[c][cp] = distance of start c to minimiser cp: transposed on the device.  nb^2 / 2 questions per batch — 46 k at config 4:
+         * with the gathered-row index of cp, a division and a remainder, inside the loop they were the better part of the 0.6 ms the
+         * device waited for this walk — hence the hoisted pointers: nothing is read through `d` in here) */
+        {
+            const double Fr = d->F[r], *Sc = d->h_S + (size_t) c * (size_t) nb, *lfc = d->lf_cand;
+            for (cp = 0; cp < c; ++cp)
+                if (lfc[cp] < Fr && Sc[cp] < cl) cl = Sc[cp];
+        }
+        pot = !(cl <= (dlm * R) * (dlm * R));
+        /* nodes between the previous candidate and this one were visited and skipped */
+        w->remaining -= (int) (cand[c] + 1 - w->idx);
+        w->idx = cand[c] + 1;
+        if (pot && d->h_flags[c]) pot = 0;                                     /* too close to a bound (mlsl.c:211-218) */
+        if (!pot) continue;
+        if (tests_at_commit) {                                                 /* mlsl.c:391-399, on the agreed view */
+            if (nla_stop_forced(d->sp)) { d->ret = NLOPT_FORCED_STOP; break; }
+            if (nla_stop_evals(stop)) { d->ret = NLOPT_MAXEVAL_REACHED; break; }
+            if (nla_stop_time(d->sp)) { d->ret = NLOPT_MAXTIME_REACHED; break; }
+        }
+        /* did this search run under the evaluation limit it would have had in the serial order? */
+        eff = mlsl_eval_limit(d);
+        if (eff > 0 && eff != d->prm.maxeval && res[g].nevals >= eff && mlsl_rerun_search(d, w, c, r, g, eff)) return -1;
+        calls = use_mma ? res[g].iterm : res[g].nevals;                        /* objective calls the search made (MMA: iterm) */
+        *stop->nevals_p += calls;                                              /* fcount, mlsl.c:246-251 */
+        if (st) { st->evals_mutation += (uint64_t) calls; ++st->accepted; }
+        d->minimized[r] = 1;
+        mlsl_trace(d->opt, res[g].f, r, 4, calls);
+        if (res[g].ret < 0) { d->ret = (nlopt_result) res[g].ret; d->search_failed = 1; return 0; }
+        lf = res[g].f;
+        /* the minimum joins the device-side set; stream-ordered, no synchronisation per minimum (room for the whole
+         * batch was made before the walk; res[] stays valid until the batch's closing synchronisation) */
+        d->h_idx[bmax + BATCH_MAX + w->nacc] = (int64_t) g;
+        d->h_lf[w->nacc] = lf;
+        d->h_lfall[g] = lf;
+        d->lf_cand[c] = lf;
+        ++w->nacc;
+        d->LF[d->nlms] = lf;
+        ord_insert(d->lord, d->nlms, d->LF, d->nlms);
+        ++d->nlms;
+        d->ret = mlsl_stop_after_search(d, lf);
+        /* (pts_update_newlm for this minimum: with the batch's other accepted minima, in one launch — mlsl_publish_minima.  A minimum
+         * whose commit ends the run updated nothing in the reference either — the stop tests come first, mlsl.c:417-425 — so it is left out.) */
+        if (d->ret != NLOPT_SUCCESS) { d->h_lfall[g] = HUGE_VAL; d->lf_cand[c] = HUGE_VAL; }
+    }
+    return 0;
+}
+
+/* the batch's accepted minima reach the points and the device-side set */
+static int mlsl_publish_minima(mlsl_dev *d, const mlsl_walk *w)
+{
+    const int nacc = w->nacc, rows = w->per * d->world, bmax = d->bmax;
+    /* pts_update_newlm (mlsl.c:180-194) for every accepted minimum of the batch at once: closest_lm_d[k] = min over the accepted
+     * minima with smaller f than point k of their distance to k — a min, so the order of the commits does not matter.  (The
+     * reference skips minimised points; their closest_lm_d is never read again, mlsl.c:200, so no flag is consulted here.) */
+    if (nacc > 0 && (nla_memcpy_h2d(d->d_lfall, d->h_lfall, sizeof(double) * (size_t) rows, d->st) ||
+                     nla_memcpy_h2d(d->d_cpd, d->cld, sizeof(double) * d->npts, d->st) ||
+                     nla_k_mlsl_colmin(d->d_D, (int) d->npts, rows, (int) d->npts, d->d_lfall, d->d_F, NULL, d->d_cpd, d->st) ||
+                     nla_memcpy_d2h(d->cld, d->d_cpd, sizeof(double) * d->npts, d->st))) MFAIL(d, "closest-minimum update failed");
+    /* the batch's accepted minima join the device-side set in acceptance order: one gather launch */
+    if (nacc > 0 && (nla_memcpy_h2d(d->d_idx + bmax + BATCH_MAX, d->h_idx + bmax + BATCH_MAX, sizeof(int64_t) * (size_t) nacc, d->st) ||
+                     nla_k_mlsl_gather_rows(d->n, d->ld, d->d_LX, d->d_idx + bmax + BATCH_MAX, nacc, d->d_LM + w->nlms0 * (size_t) d->ld, d->st) ||
+                     nla_memcpy_h2d(d->d_LF + w->nlms0, d->h_lf, sizeof(double) * (size_t) nacc, d->st))) MFAIL(d, "minimum store failed");
+    if (nla_stream_sync(d->st)) MFAIL(d, "minimum store failed");
+    return 0;
+}
+
+static int mlsl_local_phase(mlsl_dev *d)
+{
+    const double t0 = nla_seconds();
+    mlsl_walk w;
+    w.R = d->R_prefactor * pow(log((double) d->npts) / d->npts, 1.0 / d->n);
+    w.idx = 0;
+    w.remaining = (int) (ceil(MLSL_GAMMA * d->npts) + 0.5);
+    while (w.idx < d->npts && w.remaining > 0 && d->ret == NLOPT_SUCCESS) {
+        mlsl_select_candidates(d, &w);
+        if (w.nb == 0) { w.idx = w.scan; w.remaining = w.rem; break; }
+        if (mlsl_agree(d) || mlsl_launch_batch(d, &w)) return -1;
+        if (d->ret != NLOPT_SUCCESS) break;                                    /* stopped in front of a host search */
+        if (mlsl_commit_batch(d, &w)) return -1;
+        if (d->search_failed) return 0;                                        /* (the reference's goto done from inside the walk) */
+        if (mlsl_publish_minima(d, &w)) return -1;
+        if (d->ret == NLOPT_SUCCESS) {
+            /* nodes scanned after the last candidate of the batch (none qualified) are visited too */
+            w.remaining -= (int) (w.scan - w.idx);
+            w.idx = w.scan;
         }
     }
+    if (mlsl_prefetch_now(d)) return -1;                                       /* (an iteration without a local search) */
+    if (d->stats) { d->stats->t_evolve_s += nla_seconds() - t0; ++d->stats->generations; }
+    return 0;
+}
+
+nlopt_result nla_mlsl_minimize(nlopt_opt opt, int n, nlopt_func f, void *f_data, const double *lb, const double *ub, double *x,
+                               double *minf, nla_stopping *stop, nlopt_opt local_opt, int Nsamples, int lds)
+{
+    mlsl_dev D;
+    nlopt_result ret;
+
+    memset(&D, 0, sizeof D);
+    if ((ret = mlsl_check_args(&D, stop, local_opt, Nsamples)) != NLOPT_SUCCESS) return ret;
+    if ((ret = mlsl_setup(&D, opt, n, f, f_data, lb, ub, stop, local_opt, lds)) != NLOPT_SUCCESS) { mfree(&D); return ret; }
+    D.ret = NLOPT_SUCCESS;
+    if (D.world > 1) {
+        const int all = nla_comm_agree_same(D.comm, 1, nla_problem_fingerprint(lds ? NLOPT_G_MLSL_LDS : NLOPT_G_MLSL, n, D.N, D.obj + 100 * (int) local_opt->algorithm, lb, ub, x, stop) + nla_params_fingerprint(opt) + nla_params_fingerprint(local_opt));
+        if (all < 0) { nla_stop_msg(stop, NLA_MSG_RANKS_DIFFER); D.ret = NLOPT_INVALID_ARGS; goto done; }
+        if (all == 0) { nla_stop_msg(stop, "nlopt_amd: another rank could not set up its MLSL device state"); D.ret = NLOPT_FAILURE; goto done; }
+    }
+    if (mlsl_first_point(&D, x)) goto devfail;
+    while (D.ret == NLOPT_SUCCESS) {
+        double t0 = nla_seconds();
+        mlsl_get_minf(&D);                                                     /* mlsl.c:347 */
+        if (mlsl_agree(&D)) goto devfail;
+        if (opt && opt->progress) { opt->progress(opt->progress_data, D.stats ? (long) D.stats->generations : 0, (long) *stop->nevals_p); t0 = nla_seconds(); }
+        if (mlsl_sampling_phase(&D, t0) || (D.ret == NLOPT_SUCCESS && mlsl_local_phase(&D))) goto devfail;
+    }
+    if (!D.search_failed) mlsl_get_minf(&D);                                   /* mlsl.c:431 */
+    if (D.best_f < HUGE_VAL) {
+        const double *src = D.best_is_lm ? D.d_LM + D.best_row * (size_t) D.ld : D.d_P + D.best_row * (size_t) D.ld;
+        *minf = D.best_f;
+        if (nla_memcpy_d2h(x, src, sizeof(double) * (size_t) n, D.st) || nla_stream_sync(D.st)) { nla_stop_msg(stop, "device engine: result read-back failed"); D.ret = NLOPT_FAILURE; }
+    }
+    goto done;
+devfail:                                   /* a phase failed with D.err set: the one place that reports it */
+    nla_stop_msg(stop, "device engine: %s", D.err);
+    D.ret = NLOPT_FAILURE;
 done:
-    if (st) st->mt_words = D.words_used;
-    if (use_cobyla) { local_opt->f = lo_f; local_opt->f_data = lo_fdata; nla_host_free(cob_x); }   /* (the wrapper's data live on this stack) */
+    if (D.stats) D.stats->mt_words = D.words_used;
+    ret = D.ret;
     mfree(&D);
-    nla_host_free(Fnew); free(res); free(res_mine); free(cand);
     return ret;
 }
