@@ -96,8 +96,16 @@ nlopt_result nlopt_amd_set_device_objective_row_data(nlopt_opt opt, size_t rows,
  * objective or an ordinary host callback (called on the caller's thread, in ascending search order within a step of the batch);
  * NLOPT_LN_COBYLA without constraints on a device objective (compiled-in or user) at a dimension the device launchers serve.  COBYLA
  * searches always run on the device here, whatever the batch size, so a search's bits do not depend on `count`.
+ * NLOPT_LN_COBYLA WITH nonlinear constraints when all of this holds: every constraint entry is a bound device block
+ * (nlopt_amd_add_*_device_mconstraint[_data] below, ABI 1 or 2 — one data block shared by all searches); the objective is a user device
+ * objective (ABI 1, 2, or 3: search i keeps reading data row i); nla_cobyla_con_serves(n, mc) with mc = inequality values + 2 x equality
+ * values (part 2).  Each step of a chunk is then: the search kernel, one launch of the objective's kernel for the waiting searches, one
+ * launch per constraint block over the chunk's rows, the search kernel again.  The result of such a search is the algorithm's own x
+ * and minf, as the reference's (which keeps the best point seen for unconstrained COBYLA only).
  *
- * Refused with NLOPT_INVALID_ARGS and an errmsg, opt and x untouched: any other algorithm; nonlinear constraints; any lb[i] == ub[i]
+ * Refused with NLOPT_INVALID_ARGS and an errmsg, opt and x untouched: any other algorithm; nonlinear constraints with LD_LBFGS or LD_MMA;
+ * with LN_COBYLA a constraint that is an ordinary host callback ("... must be device blocks"), a compiled-in or host objective beside
+ * constraints, an (n, mc) the constrained launcher does not serve, a device layer without that launcher; any lb[i] == ub[i]
  * (fixed coordinates are not eliminated here: out of scope); a communicator (nlopt_amd_set_comm); count == 0 or a NULL array;
  * count > INT_MAX; a start outside the box; an ABI-3 objective with count > rows.  NLOPT_FAILURE: no device.
  *
@@ -109,8 +117,10 @@ nlopt_result nlopt_amd_set_device_objective_row_data(nlopt_opt opt, size_t rows,
  * the true maximum.  "amd_exact_dot" as for a lone run.
  *
  * Contract: search i returns exactly what nlopt_optimize on the same optimiser returns from x_i alone — x and minf bit for bit, the
- * result code, the evaluation count.  (LN_COBYLA, whose lone run is the host algorithm: what a batch of one through this entry
- * returns.)  With an ABI-3 objective: what nlopt_optimize returns for the same model under the ABI-2 macro with data block i.
+ * result code, the evaluation count.  (LN_COBYLA without constraints, whose lone run is the host algorithm: what a batch of one through
+ * this entry returns.  LN_COBYLA with constraint blocks: the lone run, provided no host twins are bound — the host algorithm then
+ * evaluates single points through the same kernels — or the twins give the kernels' bits.)  With an ABI-3 objective: what
+ * nlopt_optimize returns for the same model under the ABI-2 macro with data block i.
  *
  * Memory: at most `cap` searches run per launch, cap chosen from the free device memory and the per-search work sizes; a larger batch
  * runs in consecutive chunks, and results do not depend on the chunking.  Parameters: "amd_batch_chunk" (0 = automatic) forces the
@@ -120,8 +130,11 @@ nlopt_result nlopt_amd_optimize_batch(nlopt_opt opt, size_t count, double *x, do
  * (nla_k_local_waiting_list, "amd_batch_host_list" = 0) instead of by the host loop.  0: the host loop built them (the default, or a
  * device layer without the launcher).  A counter of its own beside nlopt_amd_stats, whose layout stays as it is. */
 uint64_t nlopt_amd_local_list_launches(const nlopt_opt opt);
+/* the last nlopt_amd_optimize_batch of opt: launches of bound constraint blocks (one per block and coroutine step of a chunk; the rows of
+ * finished searches are part of every launch).  0: an unconstrained batch.  A counter of its own, like the one above. */
+uint64_t nlopt_amd_batch_constraint_launches(const nlopt_opt opt);
 
-/* ---- user-supplied device constraints (NLOPT_GN_ISRES evaluates them on the device) --------------------------------
+/* ---- user-supplied device constraints (NLOPT_GN_ISRES and batched NLOPT_LN_COBYLA evaluate them on the device) ----
  * code_object / name: a gfx950 code object whose source describes a block of m constraint values with
  * NLOPT_AMD_DEVICE_CONSTRAINTS(name, ...) of include/nlopt_amd_device.h; `name` selects the kernel <name>_coneval.  Each call
  * appends ONE ordinary m-dimensional constraint, exactly as nlopt_add_inequality_mconstraint / nlopt_add_equality_mconstraint
@@ -681,6 +694,32 @@ size_t nla_cobyla_save_bytes(int n);                           /* per search, of
 int nla_k_cobyla_batch_ext(int n, int ld, int count, const double *lb, const double *ub, const double *dx, double *X,
                            double *work, const nla_cobyla_params *params, nla_lbfgs_result *out,
                            const nla_local_ext *ext, void *stream);
+/* The coroutine once more, WITH NONLINEAR CONSTRAINTS whose values come from outside this library (hip/cobyla_con.hip): replaces
+ * cobyla_minimize with m > 0 or p > 0 (cobyla.c:181-271, func_wrap :81-127) for `count` starts at once.  Contract, arguments and results
+ * of nla_k_cobyla_batch_ext, and beside them:
+ *   mi, me    scalar inequality / equality values per search (uniform over the batch); mc = mi + 2 me rows stand in front of the
+ *             bound rows
+ *   EC        count x ldc doubles (ldc >= mi + me): before a launch with resume = 1 the caller has written, for every search in state
+ *             1, the mi inequality values and then the me equality values at row `inst` of EX into row `inst` of EC — beside
+ *             EF[inst], and like it never sign-flipped by a maximisation
+ *   tol       mi + me doubles by column of EC: a row may be violated by that much when the stop value is tested (cobyla.c:598); both
+ *             rows of an equality value take its tolerance
+ *   rowmap    mc ints: row k of the search reads column c = rowmap[k] >= 0 ? rowmap[k] : -rowmap[k] - 1 of EC, negated when
+ *             rowmap[k] < 0.  The reference's order (cobyla.c:106-119): rowmap[k] = -(k + 1) for k < mi (a row is -g), then per
+ *             equality BLOCK of b values at columns c0 .. c0 + b - 1: c0 .. c0 + b - 1 (+h), then -(c0 + 1) .. -(c0 + b) (-h).
+ *             Every entry must name a column < mi + me: the kernel does not check it.
+ * The result is the algorithm's own point and value, not the best point seen (the reference memoizes unconstrained runs only,
+ * optimize.c:485-506).  Serves nla_cobyla_con_serves(n, mc): 1 <= n <= NLA_COBYLA_GLOBAL_MAX_N, mc >= 1 and the search's vectors for
+ * 2n + mc rows within 64 KiB of LDS (mc <= 175 at n = 256, <= 1200 at n = 8).  `work` holds nla_cobyla_con_work_doubles(n, mc, count)
+ * doubles, ext->save nla_cobyla_con_save_bytes(n, mc) bytes per search.  Refuses with hipErrorInvalidValue, launching nothing: (n, mc)
+ * not served, mi or me negative, ld < n, ldc < mi + me, or a NULL pointer among work, params, out, X, lb, ub, ext, ext->req / EX / EF /
+ * save, EC, tol, rowmap; count <= 0 returns 0. */
+int nla_cobyla_con_serves(int n, int mc);
+size_t nla_cobyla_con_work_doubles(int n, int mc, int count);  /* doubles of `work` for `count` searches (0 when not served) */
+size_t nla_cobyla_con_save_bytes(int n, int mc);               /* per search, of nla_local_ext.save (0 when not served) */
+int nla_k_cobyla_batch_ext_con(int n, int ld, int count, const double *lb, const double *ub, const double *dx, double *X,
+                               double *work, const nla_cobyla_params *params, nla_lbfgs_result *out, const nla_local_ext *ext,
+                               int mi, int me, int ldc, const double *EC, const double *tol, const int32_t *rowmap, void *stream);
 
 /* replaces: mma_minimize (mma.c:146-449) with m = 0 for `count` independent starts at once, one workgroup per start, outer
  * and inner iterations on the device (the 0-dimensional dual "solve" is dual_func's closed form, mma.c:58-137).  X: count x

@@ -200,6 +200,8 @@ def lib():
     L.nlopt_amd_optimize_batch.argtypes = [vp, C.c_size_t, dpp, dpp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.nlopt_amd_local_list_launches.argtypes = [vp]
     L.nlopt_amd_local_list_launches.restype = C.c_uint64
+    L.nlopt_amd_batch_constraint_launches.argtypes = [vp]
+    L.nlopt_amd_batch_constraint_launches.restype = C.c_uint64
     if hasattr(L, "nla_k_local_waiting_list"):  # (not in the emulated device layer either: the host loop builds the list there)
         L.nla_k_local_waiting_list.argtypes = [vp, C.c_int, vp, vp, vp]
     if hasattr(L, "nla_k_isres_eval_cv"):       # (not in the emulated device layer: no code object loads there, so nothing needs it)
@@ -625,12 +627,19 @@ class Opt:
         """bind a block of m user-supplied device constraints g_j(x) <= 0 (include/nlopt_amd_device.h): kernel <name>_coneval of the
         code object; host_twin(x) -> sequence of m values is what the host paths call; tol: scalar or m tolerances (None: zeros);
         data (numpy array or bytes): what an ABI-2 block (NLOPT_AMD_DEVICE_CONSTRAINTS_DATA, kernel <name>_coneval_d) reads, copied
-        to the device at the call"""
+        to the device at the call.  NLOPT_GN_ISRES evaluates the block for a whole population per launch; optimize_batch with
+        LN_COBYLA (a user device objective, every constraint a bound block) evaluates it for all searches of a chunk per step; every
+        other path sees host_twin, or single points through the kernel"""
         return self._add_device_constraints(False, code_object, name, m, host_twin, tol, data)
 
     def add_equality_device_constraints(self, code_object, name, m, host_twin=None, tol=None, data=None):
         """... the same as equality constraints h_j(x) == 0"""
         return self._add_device_constraints(True, code_object, name, m, host_twin, tol, data)
+
+    def batch_constraint_launches(self):
+        """the last optimize_batch of this optimiser: launches of bound constraint blocks (one per block and coroutine step of a chunk;
+        0 for an unconstrained batch)"""
+        return self._L.nlopt_amd_batch_constraint_launches(self._h)
 
     def device_constraint_count(self):
         return self._L.nlopt_amd_device_constraint_count(self._h)
@@ -697,6 +706,8 @@ class Opt:
 
     def optimize_batch(self, X0):
         """nlopt_amd_optimize_batch: one local search (LD_LBFGS, LD_MMA, LN_COBYLA) from every row of X0, side by side on the device.
+        Nonlinear constraints are served for LN_COBYLA on a user device objective when every one of them is a bound device block
+        (add_inequality_device_constraints / add_equality_device_constraints); anything else with constraints is refused.
         Returns (X, minf, results, numevals): the minimisers (count, n) and per search its value, nlopt_result and evaluation count.
         The call's own result is in last_optimize_result(); a negative one other than FORCED_STOP raises."""
         X = np.array(X0, dtype=np.float64).reshape(-1, self.n)

@@ -8,7 +8,15 @@
  *
  * What this file adds: the checks (everything is refused before anything is touched), the direction of optimisation, the chunks —
  * at most `cap` searches per launch, cap from the free device memory — and, for a row-data objective (ABI 3, userobj.c), the first
- * data row of each chunk. */
+ * data row of each chunk.
+ *
+ * Nonlinear constraints.  Served: NLOPT_LN_COBYLA on a user device objective (ABI 1, 2 or 3) when EVERY constraint entry is a bound device
+ * block (usercon.c; ABI 1 or 2, one data block shared by all searches) and the constrained launcher (hip/cobyla_con.hip) serves
+ * (n, mc = inequality values + 2 x equality values).  The context then runs every step as: the search kernel, the objective's kernel
+ * for the waiting searches, one launch per block over the chunk's rows, the search kernel again (local_ctx.c).  Refused: LD_LBFGS /
+ * LD_MMA with constraints, a constraint that is a host callback, a compiled-in or host objective with constraints, (n, mc) beyond the
+ * launcher, a device layer without it.  Contract: search i is the lone nlopt_optimize(LN_COBYLA) of the same optimiser from x_i —
+ * cobyla_host.c, which with no host twins bound evaluates single points through the same kernels. */
 #include "nla_internal.h"
 #include <limits.h>
 #include <math.h>
@@ -34,8 +42,10 @@ nlopt_result nlopt_amd_optimize_batch(nlopt_opt opt, size_t count, double *x, do
     double dummy;
     size_t first, per, budget, cap;
     unsigned n, i;
-    int rc, on_device, total = 0;
+    int rc, on_device, total = 0, ncon = 0, mi = 0, me = 0;
     int64_t rows;
+    nla_usercon **con = NULL;
+    double *con_tol = NULL;
 
     if (!opt) return NLOPT_INVALID_ARGS;
     nla_unset_errmsg(opt);
@@ -51,7 +61,36 @@ nlopt_result nlopt_amd_optimize_batch(nlopt_opt opt, size_t count, double *x, do
         nla_set_errmsg(opt, "nlopt_amd_optimize_batch serves NLOPT_LD_LBFGS, NLOPT_LD_MMA and NLOPT_LN_COBYLA, not %s", nlopt_algorithm_to_string(opt->algorithm));
         return NLOPT_INVALID_ARGS;
     }
-    if (opt->m > 0 || opt->p > 0) { nla_set_errmsg(opt, "nlopt_amd_optimize_batch: nonlinear constraints are not served"); return NLOPT_INVALID_ARGS; }
+    if (opt->m > 0 || opt->p > 0) {
+        unsigned j;
+        size_t vi = 0, ve = 0;
+        if (opt->algorithm != NLOPT_LN_COBYLA) {
+            nla_set_errmsg(opt, "nlopt_amd_optimize_batch: nonlinear constraints are served for NLOPT_LN_COBYLA only, not for %s", nlopt_algorithm_to_string(opt->algorithm));
+            return NLOPT_INVALID_ARGS;
+        }
+        for (j = 0; j < opt->m + opt->p; ++j) {
+            const nla_constraint *cj = j < opt->m ? opt->fc + j : opt->h + (j - opt->m);
+            if (!nla_usercon_of(cj)) {
+                nla_set_errmsg(opt, "nlopt_amd_optimize_batch: nonlinear constraints of a batch must be device blocks (nlopt_amd_add_*_device_mconstraint): %s constraint %u is a host callback",
+                               j < opt->m ? "inequality" : "equality", j < opt->m ? j : j - opt->m);
+                return NLOPT_INVALID_ARGS;
+            }
+            *(j < opt->m ? &vi : &ve) += cj->m;
+        }
+        if (!nla_userobj_is_adapter(opt->f)) {
+            nla_set_errmsg(opt, "nlopt_amd_optimize_batch: nonlinear constraints are served with a user device objective (nlopt_amd_set_min/max_device_objective) only");
+            return NLOPT_INVALID_ARGS;
+        }
+        if (!nla_cobyla_con_has_launcher()) {
+            nla_set_errmsg(opt, "nlopt_amd_optimize_batch: this device layer has no LN_COBYLA launcher for nonlinear constraints");
+            return NLOPT_INVALID_ARGS;
+        }
+        if (vi > 100000 || ve > 100000 || !nla_cobyla_con_serves((int) n, (int) (vi + 2 * ve))) {
+            nla_set_errmsg(opt, "nlopt_amd_optimize_batch: no device LN_COBYLA launcher serves n = %u with %zu inequality and %zu equality values", n, vi, ve);
+            return NLOPT_INVALID_ARGS;
+        }
+        ncon = (int) (opt->m + opt->p); mi = (int) vi; me = (int) ve;
+    }
     if (opt->comm) { nla_set_errmsg(opt, "nlopt_amd_optimize_batch: a communicator is set (nlopt_amd_set_comm): multi-rank batches are not served"); return NLOPT_INVALID_ARGS; }
     for (i = 0; i < n; ++i)
         if (opt->lb[i] == opt->ub[i]) {
@@ -82,6 +121,18 @@ nlopt_result nlopt_amd_optimize_batch(nlopt_opt opt, size_t count, double *x, do
     if (opt->algorithm == NLOPT_LD_MMA && (rc = nla_mma_read_params(opt, &mma))) return (nlopt_result) rc;
     if (nla_dev_count() <= 0) { nla_set_errmsg(opt, "nlopt_amd: no HIP device visible (this library has no CPU fallback)"); return NLOPT_FAILURE; }
 
+    if (ncon) {                                          /* the blocks and their tolerances in the reference's order (cobyla.c:242-251) */
+        unsigned j, k, t = 0;
+        con = (nla_usercon **) malloc(sizeof *con * (size_t) ncon);
+        con_tol = (double *) malloc(sizeof(double) * (size_t) (mi + me));
+        if (!con || !con_tol) { free(con); free(con_tol); nla_set_errmsg(opt, "out of memory"); return NLOPT_OUT_OF_MEMORY; }
+        for (j = 0; j < opt->m + opt->p; ++j) {
+            const nla_constraint *cj = j < opt->m ? opt->fc + j : opt->h + (j - opt->m);
+            con[j] = nla_usercon_of(cj);
+            for (k = 0; k < cj->m; ++k) con_tol[t++] = cj->tol ? cj->tol[k] : 0.;
+        }
+    }
+
     /* from here on the run: what nlopt_optimize does in front of a lone search */
     nlopt_set_force_stop(opt, 0);
     opt->force_stop_child = NULL;
@@ -91,10 +142,13 @@ nlopt_result nlopt_amd_optimize_batch(nlopt_opt opt, size_t count, double *x, do
     nla_evaluator_resolve(&ev, opt, opt->f, opt->f_data);
     nla_local_params_from_stop(&prm, &stop);
     spec.ev = &ev; spec.n = (int) n; spec.mma = &mma;
+    opt->batch_con_launches = 0;
+    spec.con = con; spec.ncon = ncon; spec.ncon_eq = ncon ? (int) opt->p : 0; spec.mi = mi; spec.me = me; spec.con_tol = con_tol;
+    spec.con_launches = &opt->batch_con_launches;
     if (opt->algorithm == NLOPT_LD_LBFGS) { prm.tolg = nlopt_get_param(opt, "tolg", 0.); spec.mf = nla_lbfgs_default_mf((int) n, (int) opt->vector_storage, stop.maxeval); }
 
     /* the chunk: what fits half of the free memory (the other half is the caller's, and the allocator's slack) */
-    per = nla_local_ctx_bytes_per_search(spec.alg, &ev, (int) n, spec.mf);
+    per = nla_local_ctx_bytes_per_search_con(spec.alg, &ev, (int) n, spec.mf, mi, me);
     budget = nla_dev_mem_free_bytes ? nla_dev_mem_free_bytes() / 2 : 0;
     if (budget == 0) budget = BATCH_FALLBACK_BUDGET;
     cap = budget / (per ? per : 1);
@@ -141,9 +195,10 @@ nlopt_result nlopt_amd_optimize_batch(nlopt_opt opt, size_t count, double *x, do
 close:
     nla_local_batch_close(&B);
 leave:
-    free(res);
+    free(res); free(con); free(con_tol);
     nla_direction_leave(opt, &dir);
     return ret;
 }
 
 uint64_t nlopt_amd_local_list_launches(const nlopt_opt opt) { return opt ? opt->local_list_launches : 0; }
+uint64_t nlopt_amd_batch_constraint_launches(const nlopt_opt opt) { return opt ? opt->batch_con_launches : 0; }

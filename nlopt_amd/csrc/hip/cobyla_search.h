@@ -7,6 +7,8 @@
  *   cobyla_ext.hip       cw_search<0, 2>: the storage of the global instance, the objective OUTSIDE the kernel — the search is a coroutine
  *                        (include/nlopt_amd.h "External evaluation") that leaves at its one evaluation point and is entered again
  *                        behind it, its scalars and its LDS block kept in a save record between the two launches (cw_saved)
+ *   cobyla_con.hip       cw_search<0, 2, 1>: that coroutine with the caller's nonlinear constraint values as rows in front of the bound
+ *                        rows (cw_user_rows)
  * The search touches its arrays only through the pointers of cw_ws. */
 #ifndef NLA_COBYLA_SEARCH_H
 #define NLA_COBYLA_SEARCH_H
@@ -105,6 +107,20 @@ struct cw_saved {
 #define CW_SAVED_DOUBLES ((sizeof(cw_saved) + 7) / 8)
 /* doubles of one search's save record: sized for a fully finite box, a whole number of 128-byte lines */
 __host__ __device__ static inline size_t cw_save_doubles(int n) { return (CW_SAVED_DOUBLES + cw_vec_doubles(n, 2 * n) + 15) & ~(size_t) 15; }
+
+/* doubles of the save record of a search with mc user rows in front of the bound rows (CON = 1, cobyla_con.hip) */
+__host__ __device__ static inline size_t cw_save_doubles_con(int n, int mc) { return (CW_SAVED_DOUBLES + cw_vec_doubles(n, 2 * n + mc) + 15) & ~(size_t) 15; }
+
+/* CON = 1: the user's nonlinear constraints (func_wrap, cobyla.c:105-119).  The caller has evaluated them at row `inst` of E.EX — the
+ * clipped, unscaled point the objective is evaluated at — and left the values in row `inst` of EC (ldc apart): the inequality values,
+ * then the equality values.  Row k < mc of the linear programme is map[k] >= 0 ? +EC[map[k]] : -EC[-map[k] - 1] (an inequality row is
+ * -g; an equality BLOCK gives its values +h, then the same block's -h); its tolerance in the feasibility test in front of the
+ * minf_max check is tol[that column] (cobyla.c:242-251).  All three arrays are read-only here. */
+struct cw_user_rows {
+    int mc, ldc;
+    const double *EC, *tol;
+    const int32_t *map;
+};
 
 #define SIM(i, j)  W.sim[(j) * W.ldn + (i)]            /* j < n: displacement of vertex j from the pole; j == n: the pole                cobyla.c:493-497 */
 #define SIMI(j, i) W.simi[(i) * W.ldn + (j)]           /* inverse of the displacement matrix */
@@ -445,26 +461,30 @@ static double cw_lds[24576];                                                    
  * tests, the search writes its point to row `inst` of E.EX, its state to its record of E.save, sets E.req[inst] = {1, 0} and RETURNS;
  * launched again with E.resume = 1 it restores that state, takes f = E.EF[inst] as delivered (the caller has applied the sign) and goes
  * on at EVAL_MEMO.  E.forced / E.timeout stand in for the abort flag, E.req[inst].state = 2 for the finished counter; OBJ, oscratch and
- * XB are not used.  Nothing in it waits: a launch runs every search to its next evaluation point or its end. */
-template <int OBJ, int GLOBAL>
+ * XB are not used.  Nothing in it waits: a launch runs every search to its next evaluation point or its end.
+ * CON = 1 (cobyla_con.hip, with GLOBAL = 2): U.mc rows of the caller's constraint values (cw_user_rows) stand in front of the bound rows,
+ * delivered with f; the result is the algorithm's own x and minf (the reference memoizes the best point of an unconstrained run only,
+ * optimize.c:485-506).  CON = 0: U is not looked at. */
+template <int OBJ, int GLOBAL, int CON = 0>
 __device__ __forceinline__ void cw_search(int n, int ld, int count, const double *__restrict__ lb, const double *__restrict__ ub,
                                           const double *__restrict__ dx_given, double *__restrict__ X, nla_cobyla_params P,
                                           nla_lbfgs_result *__restrict__ out, double *cw_lds, double *gw, lb_shared &S, double *oscratch, lb_exact_buf &XB,
-                                          const nla_local_ext &E = nla_local_ext())
+                                          const nla_local_ext &E = nla_local_ext(), const cw_user_rows &U = cw_user_rows())
 {
     constexpr bool EXT = GLOBAL == 2;
+    const int mc = CON ? U.mc : 0;                                /* the user's rows: in front of the bound rows */
     const int inst = blockIdx.x, lane = threadIdx.x;
     if (inst >= count) return;
     /* the coroutine: a launch that resumes concerns the searches that wait for their value (state 1) — a finished one (2) stays as it
      * is.  (Every lane reads the same word, and a barrier stands between this read and the store that ends the launch.) */
     if (EXT && E.resume && E.req[inst].state != 1) return;
     const bool resumed = EXT && E.resume;
-    cw_saved *sv = EXT ? (cw_saved *) ((double *) E.save + (size_t) inst * cw_save_doubles(n)) : nullptr;
+    cw_saved *sv = EXT ? (cw_saved *) ((double *) E.save + (size_t) inst * (CON ? cw_save_doubles_con(n, mc) : cw_save_doubles(n))) : nullptr;
     double *svec = EXT ? (double *) sv + CW_SAVED_DOUBLES : nullptr;
     double *x0 = X + (size_t) inst * ld;
     const double alpha = .25, beta = 2.1, gamma_ = .5, delta = 1.1;
     enum { EVAL_PRE, EVAL_MEMO, EVAL_POST, POLE, TRUST_STEP, JUDGE, SHRINK, FINISH_POLE, FINISH_HERE, FINISHED };
-    int i, j, k, m = 0;
+    int i, j, k, m = mc;
 
     /* the number of rows first: the finite bounds (cobyla.c:233-241) */
     int fixed = 0;
@@ -617,11 +637,15 @@ __device__ __forceinline__ void cw_search(int n, int ld, int count, const double
             int outside = 0;
             for (j = lane; j < n; j += CW_LANES) if (W.xev[j] < lb[j] || W.xev[j] > ub[j]) outside = 1;
             outside = lb_block_isum(outside, S);
-            if (!outside && f < bestf) { bestf = f; for (j = lane; j < n; j += CW_LANES) W.bestx[j] = W.xev[j]; }
+            if (!CON && !outside && f < bestf) { bestf = f; for (j = lane; j < n; j += CW_LANES) W.bestx[j] = W.xev[j]; }
         }
         /* the box as rows at the UNclipped scaled point (cobyla.c:112-121) */
         {
-            int off = 0;
+            int off = mc;
+            if (CON) {                                            /* the user's values at W.xev, with the reference's signs (cobyla.c:106-119) */
+                const double *ec = U.EC + (size_t) inst * U.ldc;
+                for (k = lane; k < mc; k += CW_LANES) { const int c = U.map[k]; W.con[k] = c >= 0 ? ec[c] : -ec[-c - 1]; }
+            }
             for (j = 0; j < n; ++j) {
                 const int fl = !cw_isinf(W.slb[j]), fu = !cw_isinf(W.sub[j]);
                 if (lane == (j & (CW_LANES - 1))) {
@@ -641,7 +665,8 @@ __device__ __forceinline__ void cw_search(int n, int ld, int count, const double
         for (k = 0; k < m; ++k) {
             const double v = -W.con[k];
             resmax = resmax >= v ? resmax : v;
-            if (v > 0.) feasible = 0;                             /* (bound rows: tolerance zero) */
+            if (CON && k < mc) { const int c = U.map[k]; if (v > U.tol[c >= 0 ? c : -c - 1]) feasible = 0; }      /* cobyla.c:598 */
+            else if (v > 0.) feasible = 0;                        /* (bound rows: tolerance zero) */
         }
         if (f < P.minf_max && feasible) { rc = CW_MINF_MAX_REACHED; go = FINISH_HERE; break; }
         CW_SYNC();

@@ -1,6 +1,6 @@
 /* local_ctx.c — the batch context of the local optimisers (nla_local_ctx): device buffers for up to `cap` simultaneous searches by
- * LD_LBFGS (hip/lbfgs_kernels.hip), LD_MMA (hip/mma_kernels.hip) or LN_COBYLA with bound constraints only (hip/cobyla_kernels.hip,
- * cobyla_global.hip, cobyla_ext.hip), and the loop that runs them.  Its callers: a lone nlopt_optimize(LD_LBFGS | LD_MMA) with count = 1
+ * LD_LBFGS (hip/lbfgs_kernels.hip), LD_MMA (hip/mma_kernels.hip) or LN_COBYLA (bound constraints only: hip/cobyla_kernels.hip,
+ * cobyla_global.hip, cobyla_ext.hip; nonlinear constraints from a user's device blocks: cobyla_con.hip), and the loop that runs them.  Its callers: a lone nlopt_optimize(LD_LBFGS | LD_MMA) with count = 1
  * (nla_local_minimize_one below, behind lbfgs_driver.c / mma_driver.c), MLSL's local phase with one workgroup or wavefront per start
  * (mlsl_driver.c), nlopt_amd_optimize_batch (batch_driver.c).  What differs between the algorithms is one entry of the table ALGS.
  *
@@ -33,7 +33,7 @@ typedef struct {
 } local_alg;
 
 /* the device buffers of a context, in bytes */
-enum { B_X, B_RES, B_REQ, B_EX, B_EG, B_EF, B_LIST, B_SAVE, B_WORK, B_IWORK, B_HIST, B_COUNT };
+enum { B_X, B_RES, B_REQ, B_EX, B_EG, B_EF, B_LIST, B_SAVE, B_WORK, B_IWORK, B_HIST, B_EC, B_COUNT };
 
 struct nla_local_ctx {
     int alg, n, ld, cap, mf;
@@ -70,6 +70,14 @@ struct nla_local_ctx {
     uint64_t *list_launches;       /* optional: steps whose list the device built */
     int32_t *d_nwait, *h_nwait;    /* the list's length: device word, pinned copy */
     int64_t row0;
+    /* LN_COBYLA with nonlinear constraints (hip/cobyla_con.hip): the bound blocks in the reference's order and the first column of each
+     * in a row of EC (B_EC: cap rows of ldc = mi + me values), the tolerances by column and the row map on the device */
+    nla_usercon **con;
+    int *con_col;
+    int ncon, mi, me, ldc;
+    double *d_con_tol;
+    int32_t *d_rowmap;
+    uint64_t *con_launches;
 };
 
 /* ---- the three algorithms ---------------------------------------------------------------------------------------------------------- */
@@ -115,6 +123,8 @@ static int cobyla_launch(nla_local_ctx *c, int obj, int count, const nla_lbfgs_p
     nla_cobyla_params M;
     memset(&M, 0, sizeof M);
     PARAMS_FROM(M, P);
+    if (c->ncon) return nla_k_cobyla_batch_ext_con(c->n, c->ld, count, c->d_lb, c->d_ub, c->d_sigma_init, c->d_X, c->d_work, &M, c->d_res, ext,
+                                                   c->mi, c->me, c->ldc, (const double *) c->d[B_EC], c->d_con_tol, c->d_rowmap, c->st);
     if (ext) return nla_k_cobyla_batch_ext(c->n, c->ld, count, c->d_lb, c->d_ub, c->d_sigma_init, c->d_X, c->d_work, &M, c->d_res, ext, c->st);
     return (cobyla_in_global_memory(c->n) ? nla_k_cobyla_batch_global : nla_k_cobyla_batch)
                (obj, c->n, c->ld, count, c->d_lb, c->d_ub, c->d_sigma_init, c->d_X, c->d_work, c->d_iwork, &M, c->d_res, c->st);
@@ -128,8 +138,9 @@ static const local_alg ALGS[] = {
 };
 
 /* THE layout: the size of every device buffer of a context for `cap` searches.  Allocation (nla_local_ctx_create) and the chunk size of
- * nlopt_amd_optimize_batch (nla_local_ctx_bytes_per_search) both read it. */
-static void local_layout(size_t b[B_COUNT], int alg, int kind, int n, int mf, int cap)
+ * nlopt_amd_optimize_batch (nla_local_ctx_bytes_per_search) both read it.  mi, me: the values of a user's constraint blocks per search
+ * (LN_COBYLA on a user's objective; 0, 0: none) — a row of EC each, and the save record and the slice sized for mi + 2 me more rows. */
+static void local_layout(size_t b[B_COUNT], int alg, int kind, int n, int mf, int cap, int mi, int me)
 {
     const local_alg *a = &ALGS[alg];
     const int ld = (n + 1) & ~1;
@@ -142,17 +153,23 @@ static void local_layout(size_t b[B_COUNT], int alg, int kind, int n, int mf, in
     }
     a->sizes(kind, n, ld, mf, cap, &b[B_WORK], &b[B_IWORK], &b[B_HIST]);
     b[B_WORK] *= sizeof(double); b[B_IWORK] *= sizeof(int); b[B_HIST] *= sizeof(double);
+    if (alg == NLA_LOCAL_COBYLA && kind == NLA_EVAL_USER && mi + me > 0 && nla_cobyla_con_has_launcher()) {
+        b[B_EC] = sizeof(double) * (size_t) (mi + me) * (size_t) cap;
+        b[B_SAVE] = nla_cobyla_con_save_bytes(n, mi + 2 * me) * (size_t) cap;
+        b[B_WORK] = sizeof(double) * nla_cobyla_con_work_doubles(n, mi + 2 * me, cap);
+    }
 }
 /* device memory one search takes in a context of algorithm alg (not in it: pinned host memory, the 8 doubles that stand for EG where no
  * gradient is delivered) */
-size_t nla_local_ctx_bytes_per_search(int alg, const nla_evaluator *ev, int n, int mf)
+size_t nla_local_ctx_bytes_per_search_con(int alg, const nla_evaluator *ev, int n, int mf, int mi, int me)
 {
     size_t b[B_COUNT], sum = 0;
     int i;
-    local_layout(b, alg, ev->kind, n, mf, 1);
+    local_layout(b, alg, ev->kind, n, mf, 1, mi, me);
     for (i = 0; i < B_COUNT; ++i) sum += b[i];
     return sum;
 }
+size_t nla_local_ctx_bytes_per_search(int alg, const nla_evaluator *ev, int n, int mf) { return nla_local_ctx_bytes_per_search_con(alg, ev, n, mf, 0, 0); }
 
 void nla_local_ctx_destroy(nla_local_ctx *c)
 {
@@ -160,6 +177,7 @@ void nla_local_ctx_destroy(nla_local_ctx *c)
     if (!c) return;
     for (i = 0; i < B_COUNT; ++i) nla_dev_free(c->d[i]);
     nla_dev_free(c->d_xtol_abs); nla_dev_free(c->d_x_weights);
+    nla_dev_free(c->d_con_tol); nla_dev_free(c->d_rowmap); free(c->con); free(c->con_col);
     nla_dev_free(c->d_ftrace); nla_dev_free(c->d_nwait); nla_host_free(c->h_nwait);
     if (c->d_done) nla_dev_free_uncached(c->d_done);
     nla_host_free(c->h_abort); nla_host_free(c->h_req); nla_host_free(c->h_x); nla_host_free(c->h_g); nla_host_free(c->h_f);
@@ -176,7 +194,40 @@ void nla_local_ctx_set_cobyla_min_batch(nla_local_ctx *c, int min_batch)
     if (c && c->alg == NLA_LOCAL_COBYLA && c->ev.kind == NLA_EVAL_DEVICE && min_batch > 0) c->cob_min_batch = min_batch;
 }
 
-/* the context of *s (nla_internal.h); NULL: out of memory, or LN_COBYLA for a host callback or a dimension no device launcher serves */
+/* the constraint blocks of *s into the context: the blocks and their columns, the tolerances and the row map (the reference's row order,
+ * cobyla.c:106-119: row k < mi is -g_k; an equality block of b values gives b rows +h, then b rows -h) on the device.  0 or -1. */
+static int con_setup(nla_local_ctx *c, const nla_local_spec *s)
+{
+    const int mc = s->mi + 2 * s->me;
+    int32_t *map = (int32_t *) malloc(sizeof(int32_t) * (size_t) mc);
+    int i, j, col = 0, row = 0, rc = -1;
+    c->con = (nla_usercon **) malloc(sizeof *c->con * (size_t) s->ncon);
+    c->con_col = (int *) malloc(sizeof(int) * (size_t) s->ncon);
+    c->d_con_tol = (double *) nla_dev_malloc(sizeof(double) * (size_t) (s->mi + s->me));
+    c->d_rowmap = (int32_t *) nla_dev_malloc(sizeof(int32_t) * (size_t) mc);
+    if (!map || !c->con || !c->con_col || !c->d_con_tol || !c->d_rowmap) goto done;
+    for (i = 0; i < s->ncon; ++i) {
+        const int b = (int) nla_usercon_m(s->con[i]);
+        c->con[i] = s->con[i]; c->con_col[i] = col;
+        if (row + (i < s->ncon - s->ncon_eq ? b : 2 * b) > mc) goto done;          /* (the blocks do not add up to mi, me) */
+        if (i < s->ncon - s->ncon_eq) for (j = 0; j < b; ++j) map[row++] = -(col + j + 1);
+        else {
+            for (j = 0; j < b; ++j) map[row++] = col + j;
+            for (j = 0; j < b; ++j) map[row++] = -(col + j + 1);
+        }
+        col += b;
+    }
+    if (row != mc || col != s->mi + s->me) goto done;
+    c->ncon = s->ncon; c->mi = s->mi; c->me = s->me; c->ldc = s->mi + s->me; c->con_launches = s->con_launches;
+    rc = nla_memcpy_h2d(c->d_con_tol, s->con_tol, sizeof(double) * (size_t) c->ldc, c->st) || nla_memcpy_h2d(c->d_rowmap, map, sizeof(int32_t) * (size_t) mc, c->st) ||
+         nla_stream_sync(c->st) ? -1 : 0;
+done:
+    free(map);
+    return rc;
+}
+
+/* the context of *s (nla_internal.h); NULL: out of memory, or LN_COBYLA for a host callback or a dimension no device launcher serves, or
+ * constraint blocks for anything but LN_COBYLA on a user's objective at an (n, mc) the constrained launcher serves */
 nla_local_ctx *nla_local_ctx_create(const nla_local_spec *s)
 {
     const int kind = s->ev->kind;
@@ -184,12 +235,14 @@ nla_local_ctx *nla_local_ctx_create(const nla_local_spec *s)
     nla_local_ctx *c;
     int i;
     if (s->alg == NLA_LOCAL_COBYLA && !nla_cobyla_device_serves(kind, s->n)) return NULL;
+    if (s->ncon > 0 && (s->alg != NLA_LOCAL_COBYLA || kind != NLA_EVAL_USER || !s->con || !s->con_tol || s->mi < 0 || s->me < 0 ||
+                        !nla_cobyla_con_device_serves(s->n, s->mi + 2 * s->me))) return NULL;
     c = (nla_local_ctx *) calloc(1, sizeof *c);
     if (!c) return NULL;
     c->alg = s->alg; c->a = &ALGS[s->alg]; c->ev = *s->ev; c->n = s->n; c->ld = (s->n + 1) & ~1; c->cap = s->cap; c->mf = s->mf;
     if (s->mma) c->mma = *s->mma;
     c->d_sigma_init = s->d_step; c->d_lb = s->d_lb; c->d_ub = s->d_ub; c->st = s->stream;
-    local_layout(b, s->alg, kind, s->n, s->mf, s->cap);
+    local_layout(b, s->alg, kind, s->n, s->mf, s->cap, s->ncon > 0 ? s->mi : 0, s->ncon > 0 ? s->me : 0);
     if (kind != NLA_EVAL_DEVICE && !b[B_EG]) b[B_EG] = sizeof(double) * 8;      /* (no gradient is ever delivered: a token) */
     for (i = 0; i < B_COUNT; ++i) if (b[i] && !(c->d[i] = nla_dev_malloc(b[i]))) goto fail;
     c->d_X = (double *) c->d[B_X]; c->d_res = (nla_lbfgs_result *) c->d[B_RES]; c->d_list = (int32_t *) c->d[B_LIST];
@@ -208,6 +261,7 @@ nla_local_ctx *nla_local_ctx_create(const nla_local_spec *s)
         c->h_list = (int32_t *) nla_host_malloc(sizeof(int32_t) * (size_t) c->cap);
         if (!c->h_req || !c->h_x || !c->h_g || !c->h_f || !c->h_list) goto fail;
     }
+    if (s->ncon > 0 && con_setup(c, s)) goto fail;
     if (s->alg == NLA_LOCAL_COBYLA) {
         /* host copies of the box and the step for the host twin (cobyla_small_batch_on_host), and from how many searches on a batch
          * runs on the device */
@@ -390,6 +444,18 @@ static int wait_watching(nla_local_ctx *c, const nla_stopping *stop)
     return rc;
 }
 
+/* LN_COBYLA with constraint blocks, behind the objective's launch of a step: every block at ALL `count` rows of EX into its columns of EC
+ * (the blocks' kernels take no list: the rows of finished searches are evaluated again and nobody reads them) */
+static int eval_constraints(nla_local_ctx *c, int count, const double *EX)
+{
+    int i, rc;
+    for (i = 0; i < c->ncon; ++i) {
+        if ((rc = nla_usercon_eval_rows(c->con[i], c->n, c->ld, (int64_t) count, EX, c->ldc, (double *) c->d[B_EC] + c->con_col[i], c->st))) return rc;
+        if (c->con_launches) ++*c->con_launches;
+    }
+    return 0;
+}
+
 /* run `count` searches from the rows already in ctx X; minimisers stay there, results come to the host.  stop (may be
  * NULL): the caller's force_stop flag and time limit, observed during the searches; live_nevals (may be NULL; host
  * objective only): incremented at every counted evaluation as the reference does (plis.c:261,391; mma.c:219,298). */
@@ -408,6 +474,8 @@ int nla_local_ctx_run(nla_local_ctx *c, int count, const nla_lbfgs_params *prm, 
         nla_local_ext E = c->ext;
         const size_t rowb = sizeof(double) * (size_t) c->n;
         if ((rc = nla_memset(E.req, 0, sizeof(nla_local_req) * (size_t) count, c->st))) return rc;
+        /* (a search that ends before its first evaluation never writes its row of EX, and the blocks are evaluated at every row) */
+        if (c->ncon && (rc = nla_memset(E.EX, 0, sizeof(double) * (size_t) c->ld * (size_t) count, c->st))) return rc;
         E.resume = 0;
         for (;;) {
             int waiting = 0;
@@ -423,6 +491,7 @@ int nla_local_ctx_run(nla_local_ctx *c, int count, const nla_lbfgs_params *prm, 
                 if (*c->h_nwait <= 0) break;
                 if ((rc = nla_userobj_evalgrad_list_rows(c->ev.user, c->n, c->ld, (int) *c->h_nwait, c->d_list, E.EX, E.EF, E.EG, c->ev.sign,
                                                          c->row0, count, c->st))) return rc;
+                if (c->ncon && (rc = eval_constraints(c, count, E.EX))) return rc;
                 E.resume = 1;
                 continue;
             }
@@ -437,6 +506,7 @@ int nla_local_ctx_run(nla_local_ctx *c, int count, const nla_lbfgs_params *prm, 
                 for (i = 0; i < count; ++i) if (c->h_req[i].state == 1) c->h_list[m++] = (c->h_req[i].want_grad & 1) ? i : -(i + 1);
                 if ((rc = nla_memcpy_h2d(c->d_list, c->h_list, sizeof(int32_t) * (size_t) m, c->st))) return rc;
                 if ((rc = nla_userobj_evalgrad_list_rows(c->ev.user, c->n, c->ld, m, c->d_list, E.EX, E.EF, E.EG, c->ev.sign, c->row0, count, c->st))) return rc;
+                if (c->ncon && (rc = eval_constraints(c, count, E.EX))) return rc;
             } else {
                 for (i = 0; i < count; ++i) {
                     const int want = c->h_req[i].want_grad;          /* bit 0: gradient wanted; bit 1: LD_MMA's uncounted call (mma.c:337-339) */
@@ -574,7 +644,7 @@ nlopt_result nla_local_minimize_one(int alg, nlopt_opt opt, int n, nlopt_func f,
                                     double *minf, nla_stopping *stop, int mf, double tolg, const nla_mma_params *mma, const double *step)
 {
     nla_evaluator ev;
-    const nla_local_spec spec = { alg, &ev, n, 1, mf, mma, NULL, NULL, NULL, NULL };      /* (box, step and stream: nla_local_batch_open) */
+    const nla_local_spec spec = { alg, &ev, n, 1, mf, mma, NULL, NULL, NULL, NULL, NULL, 0, 0, 0, 0, NULL, NULL };   /* (box, step and stream: nla_local_batch_open) */
     nla_lbfgs_params prm;
     nla_lbfgs_result res;
     char err[200];

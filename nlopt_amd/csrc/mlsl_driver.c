@@ -733,7 +733,8 @@ static nlopt_result mlsl_setup(mlsl_dev *d, nlopt_opt opt, int n, nlopt_func f, 
     } else {
         const int use_mma = d->local == MLSL_MMA;
         const nla_local_spec spec = { d->local == MLSL_DEV_COBYLA ? NLA_LOCAL_COBYLA : use_mma ? NLA_LOCAL_MMA : NLA_LOCAL_LBFGS, &d->ev, n, d->batch,
-                                      nla_lbfgs_default_mf(n, (int) local_opt->vector_storage, 0), use_mma ? &d->mma : NULL, d->d_dx, d->d_lb, d->d_ub, d->st };
+                                      nla_lbfgs_default_mf(n, (int) local_opt->vector_storage, 0), use_mma ? &d->mma : NULL, d->d_dx, d->d_lb, d->d_ub, d->st,
+                                      NULL, 0, 0, 0, 0, NULL, NULL };      /* (MLSL strips its local optimiser's nonlinear constraints, options.c:824-846) */
         d->lb = nla_local_ctx_create(&spec);
         if (d->lb && nla_local_ctx_set_options(d->lb, nla_exact_mode_for(opt, local_opt, &d->ev), local_opt->xtol_abs, local_opt->x_weights)) { nla_local_ctx_destroy(d->lb); d->lb = NULL; }
         /* (LD_LBFGS only: LD_MMA's launches are half as long as the distance pass beside them — behind a gate it ends after them and holds the

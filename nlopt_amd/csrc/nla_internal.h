@@ -87,6 +87,7 @@ struct nlopt_opt_s {
     struct nla_userobj *userobj;    /* user-supplied device objective (userobj.c): this optimiser's share of the kernel (reference counted) + its data */
     int dev_sign;                   /* -1 while a maximisation runs on a device objective without the host flip wrapper */
     uint64_t local_list_launches;   /* nlopt_amd_optimize_batch: steps whose waiting list the device built (nlopt_amd_local_list_launches) */
+    uint64_t batch_con_launches;    /* nlopt_amd_optimize_batch: launches of bound constraint blocks (nlopt_amd_batch_constraint_launches) */
 };
 
 /* ---- how an objective is evaluated ----------------------------------------------------------------------- */
@@ -123,6 +124,7 @@ nla_usercon *nla_usercon_retain(nla_usercon *u);
 void nla_usercon_release(nla_usercon *u);
 int nla_usercon_is_adapter(nlopt_mfunc mf);
 nla_usercon *nla_usercon_of(const nla_constraint *c);       /* the block behind an adapter-owned entry, else NULL */
+unsigned nla_usercon_m(const nla_usercon *u);               /* the values of a block */
 /* one constraint entry of opt at one point, through the entry's own callback: the values every host path gets (the kernel-level tests
  * read a bound block's single-point path with it) */
 int nla_constraint_eval(const nlopt_opt opt, int equality, unsigned index, unsigned n, const double *x, double *result);
@@ -293,6 +295,13 @@ typedef struct {
     const double *d_step;               /* LD_MMA, LN_COBYLA: the initial step on the device, or NULL = the default step of every start (options.c:921-946) */
     const double *d_lb, *d_ub;          /* the box on the device (uploaded before the call: LN_COBYLA reads it back) */
     void *stream;
+    /* LN_COBYLA with nonlinear constraints from bound device blocks (hip/cobyla_con.hip; nlopt_amd_optimize_batch only): the blocks in
+     * the reference's order — the inequality blocks, then the ncon_eq equality blocks —, their mi inequality and me equality values in
+     * all, the mi + me tolerances in that order (host).  ncon == 0: none. */
+    nla_usercon *const *con;
+    int ncon, ncon_eq, mi, me;
+    const double *con_tol;
+    uint64_t *con_launches;             /* optional: incremented per launch of a block */
 } nla_local_spec;
 nla_local_ctx *nla_local_ctx_create(const nla_local_spec *spec);
 void nla_local_ctx_set_cobyla_min_batch(nla_local_ctx *c, int min_batch);
@@ -314,6 +323,17 @@ static inline int nla_cobyla_ext_serves(int n)
 {
     return nla_k_cobyla_batch_ext && nla_cobyla_ext_work_doubles && nla_cobyla_save_bytes && n >= 1 && n <= NLA_COBYLA_GLOBAL_MAX_N;
 }
+/* ... and with the values of a user's constraint blocks as rows (hip/cobyla_con.hip), reached the same way: a device layer without it
+ * refuses such batches.  1: the launcher is there and serves n variables with mc = mi + 2 me user rows. */
+extern __typeof(nla_k_cobyla_batch_ext_con) nla_k_cobyla_batch_ext_con __attribute__((weak));
+extern __typeof(nla_cobyla_con_serves) nla_cobyla_con_serves __attribute__((weak));
+extern __typeof(nla_cobyla_con_work_doubles) nla_cobyla_con_work_doubles __attribute__((weak));
+extern __typeof(nla_cobyla_con_save_bytes) nla_cobyla_con_save_bytes __attribute__((weak));
+static inline int nla_cobyla_con_has_launcher(void)
+{
+    return nla_k_cobyla_batch_ext_con && nla_cobyla_con_serves && nla_cobyla_con_work_doubles && nla_cobyla_con_save_bytes;
+}
+static inline int nla_cobyla_con_device_serves(int n, int mc) { return nla_cobyla_con_has_launcher() && nla_cobyla_con_serves(n, mc); }
 /* 1: a device launcher serves LN_COBYLA for this kind of objective and n — the LDS or the global-memory kernel for a compiled-in one,
  * the coroutine for a user's kernel, none for a host callback */
 static inline int nla_cobyla_device_serves(int kind, int n)
@@ -329,6 +349,7 @@ extern __typeof(nla_dev_mem_free_bytes) nla_dev_mem_free_bytes __attribute__((we
 int nla_local_ctx_set_device_list(nla_local_ctx *c, int on, uint64_t *launches /* incremented per step, or NULL */);
 void nla_local_ctx_set_row0(nla_local_ctx *c, int64_t row0);
 size_t nla_local_ctx_bytes_per_search(int alg, const nla_evaluator *ev, int n, int mf);   /* device memory one search of a context takes */
+size_t nla_local_ctx_bytes_per_search_con(int alg, const nla_evaluator *ev, int n, int mf, int mi, int me);   /* ... with mi + me constraint values */
 /* the context nla_local_run_batch runs on: stream, the box (and LD_MMA's / LN_COBYLA's initial step) on the device, the options of the
  * run.  spec: alg, ev, n, cap, mf, mma (the stream, the box and the step on the device are set by the call from lb, ub, step: host arrays
  * of n, step optional).  nla_local_batch_close frees everything it holds. */

@@ -87,6 +87,7 @@ static void adapter(unsigned m, double *result, unsigned n, const double *x, dou
 }
 int nla_usercon_is_adapter(nlopt_mfunc mf) { return mf == adapter; }
 nla_usercon *nla_usercon_of(const nla_constraint *c) { return c && c->mf == adapter ? (nla_usercon *) c->f_data : NULL; }
+unsigned nla_usercon_m(const nla_usercon *u) { return u ? u->m : 0; }
 
 /* the values of constraint entry `index` (of the inequality or the equality list) at x, through the entry's own callback — what
  * every host path gets; for a bound block without a twin that is one point through its kernel.  0, or -1: no such entry.  (tests) */

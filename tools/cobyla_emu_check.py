@@ -160,6 +160,89 @@ def run_ext(L, n, starts, lo, hi, evaluate, xtol_rel=1e-6, maxeval=0, ftol_rel=0
                 nevals=[r.nevals for r in res], asked=asked, finished_at=finished_at, seen=seen, launches=step + 1)
 
 
+OUT_CON = os.path.join(ROOT, "tools", "_build", "libcobyla_con_emu.so")
+
+
+def build_con():
+    """hip/cobyla_con.hip (the coroutine with the caller's nonlinear constraint values as rows in front of the bound rows) the same
+    way: tests/test_cobyla_con_emu.py"""
+    return build("cobyla_con.hip", OUT_CON)
+
+
+def con_bind(L):
+    vp = C.c_void_p
+    L.nla_cobyla_con_serves.restype = C.c_int; L.nla_cobyla_con_serves.argtypes = [C.c_int, C.c_int]
+    L.nla_cobyla_con_work_doubles.restype = C.c_size_t; L.nla_cobyla_con_work_doubles.argtypes = [C.c_int] * 3
+    L.nla_cobyla_con_save_bytes.restype = C.c_size_t; L.nla_cobyla_con_save_bytes.argtypes = [C.c_int, C.c_int]
+    L.nla_k_cobyla_batch_ext_con.restype = C.c_int
+    L.nla_k_cobyla_batch_ext_con.argtypes = [C.c_int] * 3 + [vp] * 5 + [C.POINTER(Params), vp, C.POINTER(Ext)] + [C.c_int] * 3 + [vp] * 4
+    return L
+
+
+def con_rowmap(mi, eq_sizes):
+    """row -> column of EC (c >= 0: +EC[c], c < 0: -EC[-c - 1]) in the reference's order (cobyla.c:106-119): the mi inequality rows
+    negated, then per equality BLOCK its values followed by the same block's values negated"""
+    rows, c0 = [-(k + 1) for k in range(mi)], mi
+    for b in eq_sizes:
+        rows += [c0 + j for j in range(b)] + [-(c0 + j + 1) for j in range(b)]
+        c0 += b
+    return np.array(rows, dtype=np.int32)
+
+
+def run_ext_con(L, n, starts, lo, hi, evaluate, mi, eq_sizes, tol=None, xtol_rel=1e-6, maxeval=0, ftol_rel=0.0, dx=None, minf_max=-np.inf,
+                forced_from=None, mem=None, max_steps=1000000):
+    """run_ext for nla_k_cobyla_batch_ext_con: evaluate(x) returns (f, the mi inequality values, the equality values block after
+    block); f goes into EF as it comes, the values into the search's row of EC.  eq_sizes: the sizes of the equality blocks; tol: mi +
+    me tolerances by column (None: zeros).  EC starts as NaN and only the rows of WAITING searches are ever written: a search that
+    read a row it did not ask for would go wrong.  Returns what run_ext returns."""
+    con_bind(L)
+    mem = mem or HostMem()
+    me = int(sum(eq_sizes))
+    mc, ldc = mi + 2 * me, max(mi + me, 1)
+    count, ld = starts.shape[0], (n + 1) & ~1
+    X = np.zeros((count, ld)); X[:, :n] = starts
+    bX, bl, bu = mem.put(X), mem.put(np.asarray(lo, dtype=np.float64)), mem.put(np.asarray(hi, dtype=np.float64))
+    bd = mem.put(np.asarray(dx, dtype=np.float64)) if dx is not None else None
+    bw = mem.alloc(8 * L.nla_cobyla_con_work_doubles(n, mc, count), 0xff)
+    bsave, breq = mem.alloc(L.nla_cobyla_con_save_bytes(n, mc) * count, 0xff), mem.put(np.zeros((count, 2), dtype=np.int32))
+    bEX, bEG, bEF = mem.put(np.full((count, ld), np.nan)), mem.put(np.full(8, np.nan)), mem.put(np.full(count, np.nan))
+    bEC = mem.put(np.full((count, ldc), np.nan))
+    btol = mem.put(np.zeros(mi + me) if tol is None else np.asarray(tol, dtype=np.float64))
+    bmap = mem.put(con_rowmap(mi, eq_sizes))
+    bo = mem.alloc(C.sizeof(Result) * count)
+    P = Params(minf_max, ftol_rel, 0.0, xtol_rel, maxeval, 0, 1.0, None, None, None)
+    E = Ext(breq.ptr, bEX.ptr, bEG.ptr, bEF.ptr, bsave.ptr, 0, 0, 0, 0)
+    asked, finished_at, seen, step = [[] for _ in range(count)], [None] * count, [], 0
+    while True:
+        E.forced = 1 if forced_from is not None and step >= forced_from else 0
+        rc = L.nla_k_cobyla_batch_ext_con(n, ld, count, bl.ptr, bu.ptr, bd.ptr if bd else None, bX.ptr, bw.ptr, C.byref(P), bo.ptr, C.byref(E),
+                                          mi, me, ldc, bEC.ptr, btol.ptr, bmap.ptr, None)
+        assert rc == 0, rc
+        mem.sync()
+        state = mem.read(breq, np.int32, 2 * count).reshape(count, 2)[:, 0]
+        seen.append(state.copy())
+        for i in range(count):
+            if state[i] == 2 and finished_at[i] is None:
+                finished_at[i] = step
+        waiting = [i for i in range(count) if state[i] == 1]
+        if not waiting:
+            break
+        assert step < max_steps
+        EX, EF = mem.read(bEX, np.float64, count * ld).reshape(count, ld), mem.read(bEF, np.float64, count)
+        EC = mem.read(bEC, np.float64, count * ldc).reshape(count, ldc)
+        for i in waiting:
+            asked[i].append(EX[i, :n].copy())
+            f, g, h = evaluate(EX[i, :n].copy())
+            EF[i] = f
+            EC[i, :mi + me] = np.concatenate([np.asarray(g, dtype=np.float64).reshape(-1), np.asarray(h, dtype=np.float64).reshape(-1)])
+        mem.write(bEF, EF); mem.write(bEC, EC)
+        E.resume = 1
+        step += 1
+    res = (Result * count).from_buffer_copy(mem.read(bo, np.uint8, C.sizeof(Result) * count).tobytes())
+    return dict(x=mem.read(bX, np.float64, count * ld).reshape(count, ld)[:, :n].copy(), f=np.array([r.f for r in res]), ret=[r.ret for r in res],
+                nevals=[r.nevals for r in res], asked=asked, finished_at=finished_at, seen=seen, launches=step + 1)
+
+
 def main():
     quick =len(sys.argv) > 1 and sys.argv[1] == "quick"
     build()
