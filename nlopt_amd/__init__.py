@@ -234,7 +234,7 @@ def lib():
     L.nla_isres_evolve2_supported.argtypes = [C.c_int]
     L.nla_k_crs_commit.argtypes = [C.c_int, C.c_int, vp, vp, vp, C.c_int, vp, vp, vp, vp]
     L.nla_k_crs_mutate.argtypes = [C.c_int, vp, vp, vp, vp, vp, vp]
-    # the launchers crs_engine.c uses on its usual path: lists as kernel arguments (host arrays), the fused commit, the doorbell,
+    # the launchers crs_pass.c uses on its usual path: lists as kernel arguments (host arrays), the fused commit, the doorbell,
     # the production form of the window launch, the column-sharded pass
     L.nla_host_malloc.argtypes = [C.c_size_t]
     L.nla_host_malloc.restype = vp

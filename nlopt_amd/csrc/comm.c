@@ -328,7 +328,7 @@ void nlopt_amd_comm_destroy(nlopt_amd_comm *c)
 /* A rank that fails in the middle of a multi-rank job where it cannot say so through the job's own exchange (the device is gone, an
  * allocation failed between two collectives) calls this before it leaves: on the shm transport every rank waiting in, or arriving at, a
  * barrier returns an error instead of waiting for it; the RCCL and callback transports have no such channel (their peers wait for the
- * transport's own timeout) — the per-pass error flag of the sharded CRS run (crs_engine.c) covers what can still be said in band. */
+ * transport's own timeout) — the per-pass error flag of the sharded CRS run (crs_pass.c) covers what can still be said in band. */
 void nla_comm_abort(nlopt_amd_comm *c)
 {
     if (c && c->shm && c->shm->h) atomic_store_explicit(&c->shm->h->aborted, 1, memory_order_release);

@@ -2,7 +2,7 @@
 (oracle/libnlopt_amd_emu.so through tests/_emu_plugin.py, in a pytest process of its own — the package holds one library per process).
 The device-resolved CRS2_LM windows are the default at every dimension; what this checks is the HOST's side of them — the driver's in-order
 walk that verifies, record by record, what every slot read from which producer (crs_driver.c), the engine's window plumbing
-(crs_engine.c: lists as kernel arguments or uploads, ticket accounting, commits) — for the golden cases and for drawn configurations
+(crs_pass.c: lists as kernel arguments or uploads, ticket accounting, commits) — for the golden cases and for drawn configurations
 with populations barely above n, every stopping rule and several window depths, against the oracle evaluation by evaluation.  The HIP
 kernels are not run here (the emulation states them sequentially: oracle/port_kernels.c)."""
 import os
@@ -52,7 +52,7 @@ print(json.dumps(out))
 
 @pytest.mark.skipif(not os.path.exists(EMU), reason="the emulated library is not built")
 def test_the_ordered_sets_upkeep_runs_inside_the_engine_call():
-    """crs_driver.c redraws its list of worst rows from the heap while the engine has a pass with the device (ops->set_idle: crs_engine.c
+    """crs_driver.c redraws its list of worst rows from the heap while the engine has a pass with the device (ops->set_idle: crs_pass.c
     calls the driver between launch and wait): over the emulated device, for windows and for conservative passes, nearly every redraw
     after the first happens there — a redraw between two launches (the list ran short because the window size jumped) stays the
     exception — and both modes end at the same minimum."""

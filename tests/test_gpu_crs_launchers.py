@@ -1,4 +1,4 @@
-"""-m gpu: the CRS2_LM launchers crs_engine.c calls on its usual path, one by one, against the CPU oracle's statements of the same
+"""-m gpu: the CRS2_LM launchers crs_pass.c calls on its usual path, one by one, against the CPU oracle's statements of the same
 contracts (oracle/port_kernels.c) through the kernel-level C-ABI — tests/test_gpu_kernels.py drives the pointer forms only.
   A  lists as kernel arguments: nla_k_crs_advance_args / _finish_args / _commit_args, and bit-identity with the pointer forms
   B  the fused commit with forwarding: nla_k_crs_advance_commit_args

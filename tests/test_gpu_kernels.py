@@ -186,7 +186,7 @@ def chain_kernel_case(L, obj, n, N, K, i0, lean=None):
     chain has rejections, accepted mutations and values landing among the worst rows again.  The chain is advanced by the launch's
     resolver wavefront (hip/crs_chain_resolver.h); a trial that becomes the new best point ends the window (control word `halt` =
     2 | (slot + 1) << 8): later slots may come back "not computed" (status.t = 0), never with a wrong point.
-    lean = "host" / "dev": the launch as crs_engine.c issues it (tests/test_gpu_crs_launchers.py) — nla_k_crs_commit_zero in front
+    lean = "host" / "dev": the launch as crs_pass.c issues it (tests/test_gpu_crs_launchers.py) — nla_k_crs_commit_zero in front
     (two accepted points of an earlier window into their rows, commit lists as host / device arrays, and the control block cleared
     behind its ticket word), then nla_k_crs_chain_lean with ctrl_is_zero = 1, W / Wf as host arrays, status / fwcnt / fwrec in pinned
     host memory.  The clearing is asserted BEFORE the window is launched."""

@@ -134,7 +134,7 @@ def test_mlsl_with_a_fixed_coordinate_over_the_ranks_matches_oracle(world, obj, 
 @pytest.mark.parametrize("world,first,env", [(1, 0, {}), (1, 15, {"NLA_CRS_UPLOAD": "1", "NLA_CRS_COPY_STATUS": "1"}), (2, 30, {}), (3, 40, {}),
                                              (1, 50, {"NLA_EMU_EVOLVE2": "1"}), (2, 65, {"NLA_EMU_EVOLVE2": "1"})])
 def test_drawn_configurations_of_the_host_drivers_over_the_emulated_device(world, first, env):
-    """CRS2_LM (whole product path incl. crs_engine.c: window factor, speculation cap, host-callback mode, the alternative list /
+    """CRS2_LM (whole product path incl. crs_engine.c / crs_pass.c: window factor, speculation cap, host-callback mode, the alternative list /
     status transports), ESCH, ISRES (with NLA_EMU_EVOLVE2 the emulated device plays the multi-start evolve's protocol — rounds of
     at most 256 individuals, forced hand-overs to the serial kernel, deviates running out mid-round — so the driver's round / refill
     / fallback loop runs) and MLSL: objective, dimension, population / samples, seed, constraints, stop value, local optimiser + tolerance + its own evaluation
@@ -145,7 +145,7 @@ def test_drawn_configurations_of_the_host_drivers_over_the_emulated_device(world
         assert d["checked"][0] == count
 
 
-# ---- CRS2_LM with the population sharded BY COORDINATE over the ranks (hip/crs_shard.hip, crs_engine.c) ---------------------------
+# ---- CRS2_LM with the population sharded BY COORDINATE over the ranks (hip/crs_shard.hip, crs_pass.c) ----------------------------
 SHARDED_CRS = [
     # obj, n, pop, seed, maxeval, extra
     ("rastrigin", 10, 100, 42, 1400, {}),                       # BASELINE config 1's shape
