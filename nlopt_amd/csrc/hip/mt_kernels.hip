@@ -380,6 +380,9 @@ __global__ __launch_bounds__(64) void mt_rankbits_kernel(const uint32_t *__restr
         if (gate && next_c <= last_c && next_end <= gb + MT_N) {
             const int keep = o.accw;                                /* (a word flushed before it is full: what follows is ORed in) */
             const long long krow = o.row;
+            /* ORed in itself: when the gate moves in the segment's LAST regeneration this is the wavefront's last word, and the next segment's
+             * wavefront may have put its bits there long ago — a plain store would wipe them out (tests/test_gpu_isres_gated.py, pop65) */
+            o.shared = 1;
             rb_flush(o, rowwords, bits, lane);
             if (keep >= 0 && krow == o.row) { o.accw = keep; o.shared = 1; }
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        /* the stores have landed before the count says so */

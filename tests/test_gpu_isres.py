@@ -61,6 +61,9 @@ def assert_same_run(a, p, exact=False):
     assert abs(a["minf"] - p["minf"]) <= RTOL * max(abs(p["minf"]), scale)
     assert np.allclose(a["x"], p["x"], rtol=1e-9, atol=1e-9 * np.abs(p["x"]).max())
     assert a["stats"]["mt_words"] == p["words"]          # same stream position: ranking sweeps and redraw counts agree
+    # no unit of the ranking pipeline gave up waiting for its bits: the driver then ranks again without gates and the run is right all the
+    # same — a gated path that never works would show in this counter alone (tests/test_gpu_isres_gated.py has the two kernels by themselves)
+    assert a["stats"]["isres_gate_timeouts"] == 0, a["stats"]
     if exact:
         assert np.array_equal(fa, fp) and np.array_equal(a["x"], p["x"])
 
@@ -104,6 +107,7 @@ def test_full_size_config3_parallel_evolve_equals_the_serial_chain():
     assert a["ret"] == b["ret"] and a["nevals"] == b["nevals"] == 150000
     assert np.array_equal(a["trace"]["f"], b["trace"]["f"]) and np.array_equal(a["x"], b["x"]) and a["minf"] == b["minf"]
     assert a["stats"]["mt_words"] == b["stats"]["mt_words"] and a["stats"]["rank_sweeps"] == 2 * 50000
+    assert a["stats"]["isres_gate_timeouts"] == 0 and b["stats"]["isres_gate_timeouts"] == 0      # both ranked through the gated kernels
     # the look-up rounds: 42 + 28 per generation if every round resolved its whole block (1024 individuals in the mutation phase since the end
     # of round 6, 256 in the variation phase), ~63 + ~37 with the windows as they are; a window prediction gone wrong (round 4: a corrupted
     # redraw statistic cost a third more rounds with identical results) shows here and nowhere else
@@ -128,6 +132,7 @@ def test_overlap_mode_changes_nothing(obj, n, pop, seed, nineq, neq, kw, monkeyp
     assert a["ret"] == b["ret"] and a["nevals"] == b["nevals"] and a["minf"] == b["minf"]
     assert np.array_equal(a["trace"]["f"], b["trace"]["f"]) and np.array_equal(a["x"], b["x"])
     assert a["stats"]["mt_words"] == b["stats"]["mt_words"] and a["stats"]["rank_sweeps"] == b["stats"]["rank_sweeps"]
+    assert a["stats"]["isres_gate_timeouts"] == 0 and b["stats"]["isres_gate_timeouts"] == 0      # (one stream: never gated; two: every gate opened)
 
 
 def test_isres_host_callback_path_is_exact():
