@@ -96,6 +96,8 @@ nlopt_result nlopt_amd_set_device_objective_row_data(nlopt_opt opt, size_t rows,
  * objective or an ordinary host callback (called on the caller's thread, in ascending search order within a step of the batch);
  * NLOPT_LN_COBYLA without constraints on a device objective (compiled-in or user) at a dimension the device launchers serve.  COBYLA
  * searches always run on the device here, whatever the batch size, so a search's bits do not depend on `count`.
+ * NLOPT_LN_NELDERMEAD (hip/nldrmd_kernels.hip; 1 <= n <= NLA_NLDRMD_MAX_N) with all three kinds of objective, an ABI-3 row-data objective
+ * included: every search, a lone one too, runs on the device — there is no host twin and no minimum batch.
  * NLOPT_LN_COBYLA WITH nonlinear constraints when all of this holds: every constraint entry is a bound device block
  * (nlopt_amd_add_*_device_mconstraint[_data] below, ABI 1 or 2 — one data block shared by all searches); the objective is a user device
  * objective (ABI 1, 2, or 3: search i keeps reading data row i); nla_cobyla_con_serves(n, mc) with mc = inequality values + 2 x equality
@@ -103,7 +105,8 @@ nlopt_result nlopt_amd_set_device_objective_row_data(nlopt_opt opt, size_t rows,
  * launch per constraint block over the chunk's rows, the search kernel again.  The result of such a search is the algorithm's own x
  * and minf, as the reference's (which keeps the best point seen for unconstrained COBYLA only).
  *
- * Refused with NLOPT_INVALID_ARGS and an errmsg, opt and x untouched: any other algorithm; nonlinear constraints with LD_LBFGS or LD_MMA;
+ * Refused with NLOPT_INVALID_ARGS and an errmsg, opt and x untouched: any other algorithm; nonlinear constraints with LD_LBFGS, LD_MMA or
+ * LN_NELDERMEAD; LN_NELDERMEAD at n > NLA_NLDRMD_MAX_N or on a device layer without its launcher;
  * with LN_COBYLA a constraint that is an ordinary host callback ("... must be device blocks"), a compiled-in or host objective beside
  * constraints, an (n, mc) the constrained launcher does not serve, a device layer without that launcher; any lb[i] == ub[i]
  * (fixed coordinates are not eliminated here: out of scope); a communicator (nlopt_amd_set_comm); count == 0 or a NULL array;
@@ -601,7 +604,7 @@ typedef struct { int32_t state, want_grad; } nla_local_req;
 typedef struct {
     nla_local_req *req;            /* count entries */
     double *EX, *EG, *EF;          /* count x ld points; count x ld gradients; count values */
-    void *save;                    /* count x nla_lbfgs_save_bytes() / nla_mma_save_bytes() / nla_cobyla_save_bytes(n) */
+    void *save;                    /* count x nla_lbfgs_save_bytes() / nla_mma_save_bytes() / nla_cobyla_save_bytes(n) / nla_nldrmd_save_bytes(n) */
     int32_t resume;                /* 0: start the searches; 1: continue those whose evaluation was delivered */
     int32_t forced, timeout;       /* the caller's nlopt_force_stop flag / maxtime verdict at this launch (stop.c:141-159) */
     int32_t pad;
@@ -720,6 +723,37 @@ size_t nla_cobyla_con_save_bytes(int n, int mc);               /* per search, of
 int nla_k_cobyla_batch_ext_con(int n, int ld, int count, const double *lb, const double *ub, const double *dx, double *X,
                                double *work, const nla_cobyla_params *params, nla_lbfgs_result *out, const nla_local_ext *ext,
                                int mi, int me, int ldc, const double *EC, const double *tol, const int32_t *rowmap, void *stream);
+
+/* ---- LN_NELDERMEAD (src/algs/neldermead/nldrmd.c), batched (hip/nldrmd_kernels.hip) ----------------------------------------------- */
+/* stopping values as nlopt_stopping holds them; exact / sign / xtol_abs / x_weights (nlopt_stop_x, stop.c:98-108) / abort / ftrace / done
+ * as for LD_LBFGS.  abort is polled in CHECK_EVAL's place (nldrmd.c:79-87) behind every 64th evaluation of a search — a poll is a read of
+ * host memory across the bus, and one per evaluation made a launch of cheap evaluations 50 times longer: 100 = NLOPT_MAXTIME_REACHED,
+ * -999 = NLOPT_FORCED_STOP. */
+#define NLA_NLDRMD_MAX_N 256
+typedef struct { double minf_max, ftol_rel, ftol_abs, xtol_rel; int32_t maxeval, exact; double sign;
+                 const double *xtol_abs, *x_weights; const int32_t *abort;
+                 double *ftrace; int64_t ftrace_cap; int32_t *done; } nla_nldrmd_params;
+int    nla_nldrmd_serves(int n);                      /* 1 for 1 <= n <= NLA_NLDRMD_MAX_N */
+size_t nla_nldrmd_work_doubles(int n, int count);     /* the simplices: one slice per search (0 when n is not served) */
+size_t nla_nldrmd_save_bytes(int n);                  /* per search, of nla_local_ext.save (0 when n is not served) */
+/* replaces: nldrmd_minimize with psi = 0 (nldrmd.c:290-314 over :106-288) as nlopt_optimize reaches it (optimize.c:886-905) for `count`
+ * independent starts at once, one WAVEFRONT per start.  obj: a compiled-in device objective (the whole search is one launch; ext NULL),
+ * or NLA_OBJ_EXTERNAL with `ext`: a coroutine by the contract of "External evaluation" above — want_grad is always 0, EF[inst] is taken
+ * as delivered (params->sign is not applied again), ext->forced / ext->timeout are consulted behind every evaluation where the
+ * reference's CHECK_EVAL consults them, params->abort and params->done are not used, a finished search stays finished through later
+ * launches and no launch waits for anything.
+ * X: count x ld, starts in, the best point seen out; dx: the initial step (n, device) or NULL = nlopt_set_default_initial_step per start
+ * (options.c:912-957); work: nla_nldrmd_work_doubles(n, count) doubles (a starting search writes what it reads); ext->save:
+ * nla_nldrmd_save_bytes(n) bytes per search.  out[i] = (f, nlopt_result, evaluations, the same, 0); a starting step that leaves two
+ * points of the initial simplex too close (nldrmd.c:156-161): (f, NLOPT_FAILURE, evaluations so far, the same, the failing dimension),
+ * no further evaluation.  With `exact` or an external objective every bit of a search is the reference's; where a search's simplex
+ * lies changes nothing.  A NaN objective value is outside that contract: the search still ends at maxeval.
+ * Refuses with hipErrorInvalidValue, launching nothing: n outside 1 .. NLA_NLDRMD_MAX_N, ld < n, a NULL pointer among lb, ub, X, work,
+ * params, out, an external objective without ext or one of ext->req / EX / EF / save, a compiled-in one with ext or an unknown id;
+ * count <= 0 returns 0.
+ * Out of scope: NLOPT_LN_SBPLX (nldrmd_minimize_ with psi > 0), LN_NELDERMEAD as MLSL's local optimiser, multi-rank batches, n > 256. */
+int nla_k_nldrmd_batch(int obj, int n, int ld, int count, const double *lb, const double *ub, const double *dx, double *X,
+                       double *work, const nla_nldrmd_params *params, nla_lbfgs_result *out, const nla_local_ext *ext, void *stream);
 
 /* replaces: mma_minimize (mma.c:146-449) with m = 0 for `count` independent starts at once, one workgroup per start, outer
  * and inner iterations on the device (the 0-dimensional dual "solve" is dual_func's closed form, mma.c:58-137).  X: count x

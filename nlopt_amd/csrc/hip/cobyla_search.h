@@ -41,6 +41,22 @@ __device__ static inline int cw_tol_reached(double vold, double vnew, double rel
     const double d = fabs(vnew - vold);
     return d < abstol || d < reltol * (fabs(vnew) + fabs(vold)) * 0.5 || (reltol > 0 && vnew == vold);
 }
+/* nlopt_set_default_initial_step for one coordinate (options.c:921-946): a quarter of the box, or 3/4 of the gap to a bound that is nearer
+ * than that (shared by every derivative-free search here: this file's, hip/nldrmd_kernels.hip) */
+__device__ static inline double cw_default_step(double lo, double hi, double xj)
+{
+    double step = __builtin_huge_val();
+    if (!cw_isinf(hi) && !cw_isinf(lo) && (hi - lo) * 0.25 < step && hi > lo) step = (hi - lo) * 0.25;
+    if (!cw_isinf(hi) && hi - xj < step && hi > xj) step = (hi - xj) * 0.75;
+    if (!cw_isinf(lo) && xj - lo < step && xj > lo) step = (xj - lo) * 0.75;
+    if (cw_isinf(step)) {
+        if (!cw_isinf(hi) && fabs(hi - xj) < fabs(step)) step = (hi - xj) * 1.1;
+        if (!cw_isinf(lo) && fabs(xj - lo) < fabs(step)) step = (xj - lo) * 1.1;
+    }
+    if (cw_isinf(step) || cw_istiny(step)) step = xj;
+    if (cw_isinf(step) || step == 0.0) step = 1;
+    return step;
+}
 /* the reference's deterministic LCG for the simplex-repair steps (cobyla.c:300-309) */
 __device__ static inline double cw_lcg_between(uint32_t *seed, double a, double b)
 {
@@ -533,19 +549,7 @@ __device__ __forceinline__ void cw_search(int n, int ld, int count, const double
         for (j = lane; j < n; j += CW_LANES) {
             double step;
             if (dx_given) step = dx_given[j];
-            else {
-                const double lo = lb[j], hi = ub[j], xj = x0[j];
-                step = __builtin_huge_val();
-                if (!cw_isinf(hi) && !cw_isinf(lo) && (hi - lo) * 0.25 < step && hi > lo) step = (hi - lo) * 0.25;
-                if (!cw_isinf(hi) && hi - xj < step && hi > xj) step = (hi - xj) * 0.75;
-                if (!cw_isinf(lo) && xj - lo < step && xj > lo) step = (xj - lo) * 0.75;
-                if (cw_isinf(step)) {
-                    if (!cw_isinf(hi) && fabs(hi - xj) < fabs(step)) step = (hi - xj) * 1.1;
-                    if (!cw_isinf(lo) && fabs(xj - lo) < fabs(step)) step = (xj - lo) * 1.1;
-                }
-                if (cw_isinf(step) || cw_istiny(step)) step = xj;
-                if (cw_isinf(step) || step == 0.0) step = 1;
-            }
+            else step = cw_default_step(lb[j], ub[j], x0[j]);
             W.step0[j] = step;
         }
         CW_SYNC();

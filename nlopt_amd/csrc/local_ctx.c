@@ -1,7 +1,8 @@
 /* local_ctx.c — the batch context of the local optimisers (nla_local_ctx): device buffers for up to `cap` simultaneous searches by
  * LD_LBFGS (hip/lbfgs_kernels.hip), LD_MMA (hip/mma_kernels.hip) or LN_COBYLA (bound constraints only: hip/cobyla_kernels.hip,
- * cobyla_global.hip, cobyla_ext.hip; nonlinear constraints from a user's device blocks: cobyla_con.hip), and the loop that runs them.  Its callers: a lone nlopt_optimize(LD_LBFGS | LD_MMA) with count = 1
- * (nla_local_minimize_one below, behind lbfgs_driver.c / mma_driver.c), MLSL's local phase with one workgroup or wavefront per start
+ * cobyla_global.hip, cobyla_ext.hip; nonlinear constraints from a user's device blocks: cobyla_con.hip) or LN_NELDERMEAD
+ * (hip/nldrmd_kernels.hip), and the loop that runs them.  Its callers: a lone nlopt_optimize(LD_LBFGS | LD_MMA | LN_NELDERMEAD) with count = 1
+ * (nla_local_minimize_one below, behind lbfgs_driver.c / mma_driver.c / nldrmd_driver.c), MLSL's local phase with one workgroup or wavefront per start
  * (mlsl_driver.c), nlopt_amd_optimize_batch (batch_driver.c).  What differs between the algorithms is one entry of the table ALGS.
  *
  * Three kinds of objective (nla_evaluator):
@@ -40,7 +41,7 @@ struct nla_local_ctx {
     const local_alg *a;
     nla_evaluator ev;
     nla_mma_params mma;            /* LD_MMA: the algorithm's own parameters (the stopping values come with each run) */
-    const double *d_sigma_init;    /* LD_MMA, LN_COBYLA: initial step on the device, or NULL */
+    const double *d_sigma_init;    /* LD_MMA, LN_COBYLA, LN_NELDERMEAD: initial step on the device, or NULL */
     void *st;
     const double *d_lb, *d_ub;
     void *d[B_COUNT];              /* the buffers of local_layout(), where it gives them a size; below and in `ext`: the same, typed */
@@ -80,7 +81,7 @@ struct nla_local_ctx {
     uint64_t *con_launches;
 };
 
-/* ---- the three algorithms ---------------------------------------------------------------------------------------------------------- */
+/* ---- the algorithms ---------------------------------------------------------------------------------------------------------------- */
 #define SIZES(name) static void name(int kind, int n, int ld, int mf, int cap, size_t *work, size_t *iwork, size_t *hist)
 static size_t lbfgs_save(int n) { (void) n; return nla_lbfgs_save_bytes(); }
 SIZES(lbfgs_sizes)
@@ -130,11 +131,24 @@ static int cobyla_launch(nla_local_ctx *c, int obj, int count, const nla_lbfgs_p
                (obj, c->n, c->ld, count, c->d_lb, c->d_ub, c->d_sigma_init, c->d_X, c->d_work, c->d_iwork, &M, c->d_res, c->st);
 }
 
+/* LN_NELDERMEAD: the simplices in `work`, nothing else; the step (NULL: the default step of every start) as LD_MMA / LN_COBYLA take it */
+static size_t nldrmd_save(int n) { return nla_nldrmd_save_bytes ? nla_nldrmd_save_bytes(n) : 0; }
+SIZES(nldrmd_sizes) { (void) kind; (void) ld; (void) mf; (void) iwork; (void) hist; *work = nla_nldrmd_work_doubles ? nla_nldrmd_work_doubles(n, cap) : 0; }
+static int nldrmd_launch(nla_local_ctx *c, int obj, int count, const nla_lbfgs_params *P, const nla_local_ext *ext)
+{
+    nla_nldrmd_params M;
+    memset(&M, 0, sizeof M);
+    PARAMS_FROM(M, P);
+    M.x_weights = P->x_weights; M.ftrace = P->ftrace; M.ftrace_cap = P->ftrace_cap;
+    return nla_k_nldrmd_batch(obj, c->n, c->ld, count, c->d_lb, c->d_ub, c->d_sigma_init, c->d_X, c->d_work, &M, c->d_res, ext, c->st);
+}
+
 static const local_alg ALGS[] = {
     /* (history columns streamed twice + the point written and read once per evaluation; mma_kernels.hip header; the point again) */
     [NLA_LOCAL_LBFGS]  = { lbfgs_save,  lbfgs_sizes,  1, lbfgs_launch,  32, 16 },
     [NLA_LOCAL_MMA]    = { mma_save,    mma_sizes,    1, mma_launch,    0,  64 },
     [NLA_LOCAL_COBYLA] = { cobyla_save, cobyla_sizes, 0, cobyla_launch, 0,  16 },   /* (never wants a gradient) */
+    [NLA_LOCAL_NLDRMD] = { nldrmd_save, nldrmd_sizes, 0, nldrmd_launch, 0,  16 },   /* (never wants a gradient; the point, as LN_COBYLA counts it) */
 };
 
 /* THE layout: the size of every device buffer of a context for `cap` searches.  Allocation (nla_local_ctx_create) and the chunk size of
@@ -227,6 +241,7 @@ done:
 }
 
 /* the context of *s (nla_internal.h); NULL: out of memory, or LN_COBYLA for a host callback or a dimension no device launcher serves, or
+ * LN_NELDERMEAD on a device layer without its launcher or at a dimension it does not serve, or
  * constraint blocks for anything but LN_COBYLA on a user's objective at an (n, mc) the constrained launcher serves */
 nla_local_ctx *nla_local_ctx_create(const nla_local_spec *s)
 {
@@ -235,6 +250,7 @@ nla_local_ctx *nla_local_ctx_create(const nla_local_spec *s)
     nla_local_ctx *c;
     int i;
     if (s->alg == NLA_LOCAL_COBYLA && !nla_cobyla_device_serves(kind, s->n)) return NULL;
+    if (s->alg == NLA_LOCAL_NLDRMD && !nla_nldrmd_device_serves(s->n)) return NULL;
     if (s->ncon > 0 && (s->alg != NLA_LOCAL_COBYLA || kind != NLA_EVAL_USER || !s->con || !s->con_tol || s->mi < 0 || s->me < 0 ||
                         !nla_cobyla_con_device_serves(s->n, s->mi + 2 * s->me))) return NULL;
     c = (nla_local_ctx *) calloc(1, sizeof *c);
@@ -643,6 +659,12 @@ void nla_local_params_from_stop(nla_lbfgs_params *prm, const nla_stopping *stop)
 nlopt_result nla_local_minimize_one(int alg, nlopt_opt opt, int n, nlopt_func f, void *f_data, const double *lb, const double *ub, double *x,
                                     double *minf, nla_stopping *stop, int mf, double tolg, const nla_mma_params *mma, const double *step)
 {
+    return nla_local_minimize_one_res(alg, opt, n, f, f_data, lb, ub, x, minf, stop, mf, tolg, mma, step, NULL);
+}
+nlopt_result nla_local_minimize_one_res(int alg, nlopt_opt opt, int n, nlopt_func f, void *f_data, const double *lb, const double *ub, double *x,
+                                        double *minf, nla_stopping *stop, int mf, double tolg, const nla_mma_params *mma, const double *step,
+                                        nla_lbfgs_result *res_out)
+{
     nla_evaluator ev;
     const nla_local_spec spec = { alg, &ev, n, 1, mf, mma, NULL, NULL, NULL, NULL, NULL, 0, 0, 0, 0, NULL, NULL };   /* (box, step and stream: nla_local_batch_open) */
     nla_lbfgs_params prm;
@@ -655,6 +677,7 @@ nlopt_result nla_local_minimize_one(int alg, nlopt_opt opt, int n, nlopt_func f,
     if (nla_local_run_batch(&spec, lb, ub, step, x, &prm, &res, stop, nla_exact_mode_for(opt, NULL, &ev),
                             ev.kind == NLA_EVAL_HOST ? stop->nevals_p : NULL, opt, err, sizeof err)) { nla_stop_msg(stop, "device engine: %s", err); return NLOPT_FAILURE; }
     *minf = res.f;
+    if (res_out) *res_out = res;
     if (ev.kind != NLA_EVAL_HOST) *stop->nevals_p += res.nevals;       /* host objective: counted call by call */
     return (nlopt_result) res.ret;
 }

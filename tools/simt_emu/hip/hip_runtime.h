@@ -55,6 +55,9 @@ static thread_local simt::Idx threadIdx, blockIdx;
 static thread_local simt::Idx blockDim, gridDim;
 
 static inline void __syncthreads() { simt::barrier().wait(); }
+/* which of the two exchange buffers the next shuffle / vote of this work-item uses: ONE turn for all of them, whatever the value's type —
+ * a turn per type would let a shuffle of ints write the buffer that the shuffle of doubles just before it is still being read from */
+static thread_local int simt_xch_turn = 0;
 template <class T> static inline T __shfl_xor(T v, int mask, int width = 64)
 {
     static_assert(sizeof(T) <= 8, "emulated shuffle: at most 8 bytes");
@@ -63,7 +66,7 @@ template <class T> static inline T __shfl_xor(T v, int mask, int width = 64)
     std::memcpy(&raw, &v, sizeof(T));
     /* two exchange buffers used in turn, ONE barrier per shuffle: buffer b is written again two shuffles later, behind the barrier
      * of the shuffle in between, which every work-item passes only after it has read b */
-    static thread_local int which = 0;
+    int &which = simt_xch_turn;
     simt::xch(which)[threadIdx.x] = raw;
     simt::barrier().wait();
     raw = simt::xch(which)[threadIdx.x ^ (unsigned) mask];
@@ -75,7 +78,7 @@ template <class T> static inline T __shfl_xor(T v, int mask, int width = 64)
 /* __all() over the 64 work-items of a wavefront (every work-item of the workgroup must call it) */
 static inline bool simt_wave_all(bool p)
 {
-    static thread_local int which = 0;
+    int &which = simt_xch_turn;
     simt::xch(which)[threadIdx.x] = p ? 1 : 0;
     simt::barrier().wait();
     bool all = true;
