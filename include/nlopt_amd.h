@@ -98,6 +98,7 @@ nlopt_result nlopt_amd_set_device_objective_row_data(nlopt_opt opt, size_t rows,
  * searches always run on the device here, whatever the batch size, so a search's bits do not depend on `count`.
  * NLOPT_LN_NELDERMEAD (hip/nldrmd_kernels.hip; 1 <= n <= NLA_NLDRMD_MAX_N) with all three kinds of objective, an ABI-3 row-data objective
  * included: every search, a lone one too, runs on the device — there is no host twin and no minimum batch.
+ * NLOPT_LN_SBPLX (hip/sbplx_kernels.hip; 1 <= n <= NLA_SBPLX_MAX_N) in the same way, with the same kinds of objective.
  * NLOPT_LN_COBYLA WITH nonlinear constraints when all of this holds: every constraint entry is a bound device block
  * (nlopt_amd_add_*_device_mconstraint[_data] below, ABI 1 or 2 — one data block shared by all searches); the objective is a user device
  * objective (ABI 1, 2, or 3: search i keeps reading data row i); nla_cobyla_con_serves(n, mc) with mc = inequality values + 2 x equality
@@ -106,7 +107,7 @@ nlopt_result nlopt_amd_set_device_objective_row_data(nlopt_opt opt, size_t rows,
  * and minf, as the reference's (which keeps the best point seen for unconstrained COBYLA only).
  *
  * Refused with NLOPT_INVALID_ARGS and an errmsg, opt and x untouched: any other algorithm; nonlinear constraints with LD_LBFGS, LD_MMA or
- * LN_NELDERMEAD; LN_NELDERMEAD at n > NLA_NLDRMD_MAX_N or on a device layer without its launcher;
+ * LN_NELDERMEAD (LN_SBPLX takes none: its setter refuses them); LN_NELDERMEAD / LN_SBPLX at n > 256 or on a device layer without its launcher;
  * with LN_COBYLA a constraint that is an ordinary host callback ("... must be device blocks"), a compiled-in or host objective beside
  * constraints, an (n, mc) the constrained launcher does not serve, a device layer without that launcher; any lb[i] == ub[i]
  * (fixed coordinates are not eliminated here: out of scope); a communicator (nlopt_amd_set_comm); count == 0 or a NULL array;
@@ -604,7 +605,7 @@ typedef struct { int32_t state, want_grad; } nla_local_req;
 typedef struct {
     nla_local_req *req;            /* count entries */
     double *EX, *EG, *EF;          /* count x ld points; count x ld gradients; count values */
-    void *save;                    /* count x nla_lbfgs_save_bytes() / nla_mma_save_bytes() / nla_cobyla_save_bytes(n) / nla_nldrmd_save_bytes(n) */
+    void *save;                    /* count x nla_lbfgs_save_bytes() / nla_mma_save_bytes() / nla_cobyla_save_bytes(n) / nla_nldrmd_save_bytes(n) / nla_sbplx_save_bytes(n) */
     int32_t resume;                /* 0: start the searches; 1: continue those whose evaluation was delivered */
     int32_t forced, timeout;       /* the caller's nlopt_force_stop flag / maxtime verdict at this launch (stop.c:141-159) */
     int32_t pad;
@@ -751,9 +752,29 @@ size_t nla_nldrmd_save_bytes(int n);                  /* per search, of nla_loca
  * Refuses with hipErrorInvalidValue, launching nothing: n outside 1 .. NLA_NLDRMD_MAX_N, ld < n, a NULL pointer among lb, ub, X, work,
  * params, out, an external objective without ext or one of ext->req / EX / EF / save, a compiled-in one with ext or an unknown id;
  * count <= 0 returns 0.
- * Out of scope: NLOPT_LN_SBPLX (nldrmd_minimize_ with psi > 0), LN_NELDERMEAD as MLSL's local optimiser, multi-rank batches, n > 256. */
+ * Out of scope: LN_NELDERMEAD as MLSL's local optimiser, multi-rank batches, n > 256. */
 int nla_k_nldrmd_batch(int obj, int n, int ld, int count, const double *lb, const double *ub, const double *dx, double *X,
                        double *work, const nla_nldrmd_params *params, nla_lbfgs_result *out, const nla_local_ext *ext, void *stream);
+
+/* ---- LN_SBPLX (src/algs/neldermead/sbplx.c over nldrmd.c), batched (hip/sbplx_kernels.hip) ------------------------------------------ */
+#define NLA_SBPLX_MAX_N 256
+typedef nla_nldrmd_params nla_sbplx_params;          /* the same stopping values and options, abort polled in the same place */
+int    nla_sbplx_serves(int n);                       /* 1 for 1 <= n <= NLA_SBPLX_MAX_N */
+size_t nla_sbplx_work_doubles(int n, int count);      /* a token (a search lives in LDS; 0 when n is not served) */
+size_t nla_sbplx_save_bytes(int n);                   /* per search, of nla_local_ext.save (0 when n is not served) */
+/* replaces: sbplx_minimize (sbplx.c:66-237) over nldrmd_minimize_ with psi = 0.25 (nldrmd.c:106-288) as nlopt_optimize reaches it
+ * (optimize.c:886-905) for `count` independent starts at once, one WAVEFRONT per start.  obj, ext, X, dx, params, the coroutine and the
+ * parity contract: as nla_k_nldrmd_batch above; the point of every request (row `inst` of EX) is the FULL x with the subspace's trial
+ * coordinates scattered into it, as the reference's subspace_func hands it to the objective.  work: nla_sbplx_work_doubles(n, count)
+ * doubles, not touched; ext->save: nla_sbplx_save_bytes(n) bytes per search.  out[i] = (f, nlopt_result, evaluations, the same, 0); a
+ * starting step too small for a subspace's initial simplex (nldrmd.c:156-161) ends the search as the reference does, with
+ * NLOPT_XTOL_REACHED (sbplx.c:162,183), and out[i].cols = 1 + the failing dimension OF THE SUBSPACE.
+ * Refuses with hipErrorInvalidValue, launching nothing, what nla_k_nldrmd_batch refuses (n outside 1 .. NLA_SBPLX_MAX_N); count <= 0
+ * returns 0.
+ * Out of scope: n > 256 (the permutation's all-pairs rank count and the LDS block are sized for it), LN_SBPLX as MLSL's local
+ * optimiser, multi-rank batches, several searches per workgroup. */
+int nla_k_sbplx_batch(int obj, int n, int ld, int count, const double *lb, const double *ub, const double *dx, double *X,
+                      double *work, const nla_sbplx_params *params, nla_lbfgs_result *out, const nla_local_ext *ext, void *stream);
 
 /* replaces: mma_minimize (mma.c:146-449) with m = 0 for `count` independent starts at once, one workgroup per start, outer
  * and inner iterations on the device (the 0-dimensional dual "solve" is dual_func's closed form, mma.c:58-137).  X: count x

@@ -168,8 +168,12 @@ static nlopt_result minimize_dispatch(nlopt_opt opt, double *x, double *minf)
     case NLOPT_LN_NELDERMEAD:                                                            /* optimize.c:886-905 */
         /* every search runs on the device (nldrmd_driver.c); a device layer without the launcher, or n beyond it: not provided, as before */
         if (nla_nldrmd_device_serves((int) n)) return nla_nldrmd_minimize(opt, (int) n, opt->f, opt->f_data, opt->lb, opt->ub, x, minf, &stop);
+        goto not_provided;
+    case NLOPT_LN_SBPLX:                                                                 /* optimize.c:886-905 */
+        if (nla_sbplx_device_serves((int) n)) return nla_sbplx_minimize(opt, (int) n, opt->f, opt->f_data, opt->lb, opt->ub, x, minf, &stop);
         /* fall through */
     default:
+    not_provided:
         nla_set_errmsg(opt, "algorithm %s is not provided by libnlopt_amd (stochastic-global hot path only)",
                        nlopt_algorithm_to_string(opt->algorithm));
         return NLOPT_INVALID_ARGS;
@@ -224,7 +228,7 @@ static int fix_applies(const nlopt_opt opt)                                     
 {
     if (fix_free_count(opt->n, opt->lb, opt->ub) == opt->n) return 0;
     return opt->algorithm == NLOPT_GN_CRS2_LM || opt->algorithm == NLOPT_GN_ISRES || opt->algorithm == NLOPT_GN_ESCH ||
-           opt->algorithm == NLOPT_LN_COBYLA || opt->algorithm == NLOPT_LN_NELDERMEAD;
+           opt->algorithm == NLOPT_LN_COBYLA || opt->algorithm == NLOPT_LN_NELDERMEAD || opt->algorithm == NLOPT_LN_SBPLX;
 }
 
 /* minimise on the reduced problem; x is shrunk on entry and expanded on return */
@@ -310,7 +314,7 @@ static int objective_stays_on_device(const nlopt_opt opt)
     if (!(nlopt_amd_objective_id(opt->f) >= 0 || nla_userobj_is_adapter(opt->f))) return 0;
     if (a == NLOPT_LD_LBFGS || a == NLOPT_G_MLSL || a == NLOPT_G_MLSL_LDS || (a >= NLOPT_GN_MLSL && a <= NLOPT_GD_MLSL_LDS)) return 1;
     if (a == NLOPT_LD_MMA) return opt->m == 0;
-    if (a == NLOPT_LN_NELDERMEAD) return !fix_applies(opt);      /* (fixed coordinates: the elimination wrapper is a host function) */
+    if (a == NLOPT_LN_NELDERMEAD || a == NLOPT_LN_SBPLX) return !fix_applies(opt);      /* (fixed coordinates: the elimination wrapper is a host function) */
     if (a == NLOPT_GN_CRS2_LM || a == NLOPT_GN_ISRES || a == NLOPT_GN_ESCH) {
         if (fix_applies(opt) || nlopt_get_param(opt, "amd_host_eval", 0) != 0) return 0;
         return a != NLOPT_GN_ISRES || nla_isres_constraints_on_device(opt->m, opt->fc, opt->p, opt->h);

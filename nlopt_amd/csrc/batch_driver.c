@@ -2,7 +2,7 @@
  *
  * The reference has no counterpart: a caller with many starts, or with many small fits of one shape, loops over nlopt_optimize.  Here
  * the loop is the batch dimension of the kernels that already serve MLSL's local phase — one workgroup (LD_LBFGS, LD_MMA) or one
- * wavefront (LN_COBYLA, LN_NELDERMEAD) per search — behind the same context a lone nlopt_optimize(LD_LBFGS | LD_MMA | LN_NELDERMEAD) runs on with count = 1
+ * wavefront (LN_COBYLA, LN_NELDERMEAD, LN_SBPLX) per search — behind the same context a lone nlopt_optimize(LD_LBFGS | LD_MMA | LN_NELDERMEAD | LN_SBPLX) runs on with count = 1
  * (local_ctx.c: nla_local_batch_open / nla_local_ctx_run).  Those kernels pick their code path from the objective, n and the
  * parameters, never from the number of searches, which is what makes search i of a batch the lone run from x_i bit for bit.
  *
@@ -57,9 +57,9 @@ nlopt_result nlopt_amd_optimize_batch(nlopt_opt opt, size_t count, double *x, do
     if (count > (size_t) INT_MAX) { nla_set_errmsg(opt, "nlopt_amd_optimize_batch: count > INT_MAX"); return NLOPT_INVALID_ARGS; }
     if (!opt->f || n == 0) { nla_set_errmsg(opt, "nlopt_amd_optimize_batch: no objective set, or n == 0"); return NLOPT_INVALID_ARGS; }
     spec.alg = opt->algorithm == NLOPT_LD_LBFGS ? NLA_LOCAL_LBFGS : opt->algorithm == NLOPT_LD_MMA ? NLA_LOCAL_MMA : opt->algorithm == NLOPT_LN_COBYLA ? NLA_LOCAL_COBYLA :
-               opt->algorithm == NLOPT_LN_NELDERMEAD ? NLA_LOCAL_NLDRMD : -1;
+               opt->algorithm == NLOPT_LN_NELDERMEAD ? NLA_LOCAL_NLDRMD : opt->algorithm == NLOPT_LN_SBPLX ? NLA_LOCAL_SBPLX : -1;
     if (spec.alg < 0) {
-        nla_set_errmsg(opt, "nlopt_amd_optimize_batch serves NLOPT_LD_LBFGS, NLOPT_LD_MMA, NLOPT_LN_COBYLA and NLOPT_LN_NELDERMEAD, not %s", nlopt_algorithm_to_string(opt->algorithm));
+        nla_set_errmsg(opt, "nlopt_amd_optimize_batch serves NLOPT_LD_LBFGS, NLOPT_LD_MMA, NLOPT_LN_COBYLA, NLOPT_LN_NELDERMEAD and NLOPT_LN_SBPLX, not %s", nlopt_algorithm_to_string(opt->algorithm));
         return NLOPT_INVALID_ARGS;
     }
     if (opt->m > 0 || opt->p > 0) {
@@ -96,6 +96,13 @@ nlopt_result nlopt_amd_optimize_batch(nlopt_opt opt, size_t count, double *x, do
         if (!nla_nldrmd_has_launcher()) { nla_set_errmsg(opt, "nlopt_amd_optimize_batch: this device layer has no LN_NELDERMEAD launcher"); return NLOPT_INVALID_ARGS; }
         if (n > NLA_NLDRMD_MAX_N || !nla_nldrmd_serves((int) n)) {
             nla_set_errmsg(opt, "nlopt_amd_optimize_batch: the device LN_NELDERMEAD launcher serves n <= %d, not n = %u", NLA_NLDRMD_MAX_N, n);
+            return NLOPT_INVALID_ARGS;
+        }
+    }
+    if (opt->algorithm == NLOPT_LN_SBPLX) {
+        if (!nla_sbplx_has_launcher()) { nla_set_errmsg(opt, "nlopt_amd_optimize_batch: this device layer has no LN_SBPLX launcher"); return NLOPT_INVALID_ARGS; }
+        if (n > NLA_SBPLX_MAX_N || !nla_sbplx_serves((int) n)) {
+            nla_set_errmsg(opt, "nlopt_amd_optimize_batch: the device LN_SBPLX launcher serves n <= %d, not n = %u", NLA_SBPLX_MAX_N, n);
             return NLOPT_INVALID_ARGS;
         }
     }

@@ -1,7 +1,7 @@
 /* local_ctx.c — the batch context of the local optimisers (nla_local_ctx): device buffers for up to `cap` simultaneous searches by
  * LD_LBFGS (hip/lbfgs_kernels.hip), LD_MMA (hip/mma_kernels.hip) or LN_COBYLA (bound constraints only: hip/cobyla_kernels.hip,
- * cobyla_global.hip, cobyla_ext.hip; nonlinear constraints from a user's device blocks: cobyla_con.hip) or LN_NELDERMEAD
- * (hip/nldrmd_kernels.hip), and the loop that runs them.  Its callers: a lone nlopt_optimize(LD_LBFGS | LD_MMA | LN_NELDERMEAD) with count = 1
+ * cobyla_global.hip, cobyla_ext.hip; nonlinear constraints from a user's device blocks: cobyla_con.hip) or LN_NELDERMEAD / LN_SBPLX
+ * (hip/nldrmd_kernels.hip, hip/sbplx_kernels.hip), and the loop that runs them.  Its callers: a lone nlopt_optimize(LD_LBFGS | LD_MMA | LN_NELDERMEAD | LN_SBPLX) with count = 1
  * (nla_local_minimize_one below, behind lbfgs_driver.c / mma_driver.c / nldrmd_driver.c), MLSL's local phase with one workgroup or wavefront per start
  * (mlsl_driver.c), nlopt_amd_optimize_batch (batch_driver.c).  What differs between the algorithms is one entry of the table ALGS.
  *
@@ -142,6 +142,17 @@ static int nldrmd_launch(nla_local_ctx *c, int obj, int count, const nla_lbfgs_p
     M.x_weights = P->x_weights; M.ftrace = P->ftrace; M.ftrace_cap = P->ftrace_cap;
     return nla_k_nldrmd_batch(obj, c->n, c->ld, count, c->d_lb, c->d_ub, c->d_sigma_init, c->d_X, c->d_work, &M, c->d_res, ext, c->st);
 }
+/* LN_SBPLX: a search lives in LDS (`work` is a token); the parameters and the step are LN_NELDERMEAD's */
+static size_t sbplx_save(int n) { return nla_sbplx_save_bytes ? nla_sbplx_save_bytes(n) : 0; }
+SIZES(sbplx_sizes) { (void) kind; (void) ld; (void) mf; (void) iwork; (void) hist; *work = nla_sbplx_work_doubles ? nla_sbplx_work_doubles(n, cap) : 0; }
+static int sbplx_launch(nla_local_ctx *c, int obj, int count, const nla_lbfgs_params *P, const nla_local_ext *ext)
+{
+    nla_sbplx_params M;
+    memset(&M, 0, sizeof M);
+    PARAMS_FROM(M, P);
+    M.x_weights = P->x_weights; M.ftrace = P->ftrace; M.ftrace_cap = P->ftrace_cap;
+    return nla_k_sbplx_batch(obj, c->n, c->ld, count, c->d_lb, c->d_ub, c->d_sigma_init, c->d_X, c->d_work, &M, c->d_res, ext, c->st);
+}
 
 static const local_alg ALGS[] = {
     /* (history columns streamed twice + the point written and read once per evaluation; mma_kernels.hip header; the point again) */
@@ -149,6 +160,7 @@ static const local_alg ALGS[] = {
     [NLA_LOCAL_MMA]    = { mma_save,    mma_sizes,    1, mma_launch,    0,  64 },
     [NLA_LOCAL_COBYLA] = { cobyla_save, cobyla_sizes, 0, cobyla_launch, 0,  16 },   /* (never wants a gradient) */
     [NLA_LOCAL_NLDRMD] = { nldrmd_save, nldrmd_sizes, 0, nldrmd_launch, 0,  16 },   /* (never wants a gradient; the point, as LN_COBYLA counts it) */
+    [NLA_LOCAL_SBPLX]  = { sbplx_save,  sbplx_sizes,  0, sbplx_launch,  0,  16 },   /* (the same) */
 };
 
 /* THE layout: the size of every device buffer of a context for `cap` searches.  Allocation (nla_local_ctx_create) and the chunk size of
@@ -241,7 +253,7 @@ done:
 }
 
 /* the context of *s (nla_internal.h); NULL: out of memory, or LN_COBYLA for a host callback or a dimension no device launcher serves, or
- * LN_NELDERMEAD on a device layer without its launcher or at a dimension it does not serve, or
+ * LN_NELDERMEAD / LN_SBPLX on a device layer without its launcher or at a dimension it does not serve, or
  * constraint blocks for anything but LN_COBYLA on a user's objective at an (n, mc) the constrained launcher serves */
 nla_local_ctx *nla_local_ctx_create(const nla_local_spec *s)
 {
@@ -251,6 +263,7 @@ nla_local_ctx *nla_local_ctx_create(const nla_local_spec *s)
     int i;
     if (s->alg == NLA_LOCAL_COBYLA && !nla_cobyla_device_serves(kind, s->n)) return NULL;
     if (s->alg == NLA_LOCAL_NLDRMD && !nla_nldrmd_device_serves(s->n)) return NULL;
+    if (s->alg == NLA_LOCAL_SBPLX && !nla_sbplx_device_serves(s->n)) return NULL;
     if (s->ncon > 0 && (s->alg != NLA_LOCAL_COBYLA || kind != NLA_EVAL_USER || !s->con || !s->con_tol || s->mi < 0 || s->me < 0 ||
                         !nla_cobyla_con_device_serves(s->n, s->mi + 2 * s->me))) return NULL;
     c = (nla_local_ctx *) calloc(1, sizeof *c);

@@ -282,7 +282,7 @@ nlopt_result nla_isres_minimize(nlopt_opt opt, int n, nlopt_func f, void *f_data
 int nla_lbfgs_default_mf(int n, int mf, int maxeval);
 
 /* ---- the batch context of the local optimisers (local_ctx.c) ---------------------------------------------------------------------- */
-enum { NLA_LOCAL_LBFGS = 0, NLA_LOCAL_MMA = 1, NLA_LOCAL_COBYLA = 2, NLA_LOCAL_NLDRMD = 3 };
+enum { NLA_LOCAL_LBFGS = 0, NLA_LOCAL_MMA = 1, NLA_LOCAL_COBYLA = 2, NLA_LOCAL_NLDRMD = 3, NLA_LOCAL_SBPLX = 4 };
 typedef struct nla_local_ctx nla_local_ctx;
 /* what a context is created from.  LN_COBYLA (bound constraints only) gives NULL for a host callback or a dimension no device launcher
  * serves (nla_cobyla_device_serves below) */
@@ -292,7 +292,7 @@ typedef struct {
     int n, cap;                         /* up to cap simultaneous searches */
     int mf;                             /* LD_LBFGS: history pairs */
     const nla_mma_params *mma;          /* LD_MMA: the algorithm's parameters (mma_driver.c reads them) */
-    const double *d_step;               /* LD_MMA, LN_COBYLA, LN_NELDERMEAD: the initial step on the device, or NULL = the default step of every start (options.c:921-946) */
+    const double *d_step;               /* LD_MMA, LN_COBYLA, LN_NELDERMEAD, LN_SBPLX: the initial step on the device, or NULL = the default step of every start (options.c:921-946) */
     const double *d_lb, *d_ub;          /* the box on the device (uploaded before the call: LN_COBYLA reads it back) */
     void *stream;
     /* LN_COBYLA with nonlinear constraints from bound device blocks (hip/cobyla_con.hip; nlopt_amd_optimize_batch only): the blocks in
@@ -348,6 +348,13 @@ extern __typeof(nla_nldrmd_work_doubles) nla_nldrmd_work_doubles __attribute__((
 extern __typeof(nla_nldrmd_save_bytes) nla_nldrmd_save_bytes __attribute__((weak));
 static inline int nla_nldrmd_has_launcher(void) { return nla_k_nldrmd_batch && nla_nldrmd_serves && nla_nldrmd_work_doubles && nla_nldrmd_save_bytes; }
 static inline int nla_nldrmd_device_serves(int n) { return nla_nldrmd_has_launcher() && nla_nldrmd_serves(n); }
+/* device LN_SBPLX (hip/sbplx_kernels.hip), the same way */
+extern __typeof(nla_k_sbplx_batch) nla_k_sbplx_batch __attribute__((weak));
+extern __typeof(nla_sbplx_serves) nla_sbplx_serves __attribute__((weak));
+extern __typeof(nla_sbplx_work_doubles) nla_sbplx_work_doubles __attribute__((weak));
+extern __typeof(nla_sbplx_save_bytes) nla_sbplx_save_bytes __attribute__((weak));
+static inline int nla_sbplx_has_launcher(void) { return nla_k_sbplx_batch && nla_sbplx_serves && nla_sbplx_work_doubles && nla_sbplx_save_bytes; }
+static inline int nla_sbplx_device_serves(int n) { return nla_sbplx_has_launcher() && nla_sbplx_serves(n); }
 /* the waiting list of a coroutine step built on the device (hip/local_list.hip) and the free-memory query nlopt_amd_optimize_batch
  * sizes its chunks from, reached the same way: without them the host loop builds the list and the chunk size is a fixed guess */
 extern __typeof(nla_k_local_waiting_list) nla_k_local_waiting_list __attribute__((weak));
@@ -391,6 +398,9 @@ nlopt_result nla_local_minimize_one_res(int alg, nlopt_opt opt, int n, nlopt_fun
 /* NLOPT_LN_NELDERMEAD (nldrmd_driver.c; reference entry nldrmd_minimize, nldrmd.c:290-314) */
 nlopt_result nla_nldrmd_minimize(nlopt_opt opt, int n, nlopt_func f, void *f_data, const double *lb, const double *ub, double *x, double *minf,
                                  nla_stopping *stop);
+/* NLOPT_LN_SBPLX (nldrmd_driver.c: the same function; reference entry sbplx_minimize, sbplx.c:66-237) */
+nlopt_result nla_sbplx_minimize(nlopt_opt opt, int n, nlopt_func f, void *f_data, const double *lb, const double *ub, double *x, double *minf,
+                                nla_stopping *stop);
 /* LD_MMA without nonlinear constraints (mma_driver.c) */
 int nla_mma_read_params(nlopt_opt opt, nla_mma_params *out);     /* optimize.c:798-815; 0 or an nlopt_result < 0 with errmsg set */
 /* NLOPT_LN_COBYLA on the host (cobyla_host.c; reference entry cobyla_minimize, cobyla.c:181-271) */

@@ -52,8 +52,9 @@ def timed_batches(o, X0, repeats):
     return float(np.median(times)), out
 
 
-def reference_loop(Y, X0, k, tmp):
-    """seconds per fit of the real reference on the C twin, its minima and its evaluations over the k fits"""
+def reference_loop(Y, X0, k, tmp, alg=None):
+    """seconds per fit of the real reference on the C twin, its minima and its evaluations over the k fits (alg: the reference's
+    algorithm, NLOPT_LN_NELDERMEAD unless given — tools/sbplx_bench.py)"""
     import nldrmd_emu_check as E
     twin = os.path.join(tmp, "libfittwin.so")
     subprocess.run(["gcc", "-O2", "-ffp-contract=off", "-fPIC", "-shared", os.path.join(ROOT, "tools", "userdata_fit_twin.c"), "-o", twin, "-lm"], check=True)
@@ -65,7 +66,7 @@ def reference_loop(Y, X0, k, tmp):
         for i in range(k):
             y = np.ascontiguousarray(Y[i])
             fd = FitData(M, T.ctypes.data, y.ctypes.data)
-            opt = R.nlopt_create(E.LN_NELDERMEAD, 3)
+            opt = R.nlopt_create(E.LN_NELDERMEAD if alg is None else alg, 3)
             R.nlopt_set_lower_bounds(opt, dp(LB)); R.nlopt_set_upper_bounds(opt, dp(UB))
             R.nlopt_set_min_objective(opt, C.cast(W.expfit_twin, C.c_void_p), C.addressof(fd))
             R.nlopt_set_xtol_rel(opt, 1e-8); R.nlopt_set_maxeval(opt, 400)

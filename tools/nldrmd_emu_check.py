@@ -30,35 +30,40 @@ class Params(C.Structure):
                 ("abort", C.c_void_p), ("ftrace", C.c_void_p), ("ftrace_cap", C.c_int64), ("done", C.c_void_p)]
 
 
-def build():
-    os.makedirs(os.path.dirname(OUT), exist_ok=True)
-    srcs = [os.path.join(HIP, "nldrmd_kernels.hip")]
-    deps = srcs + [os.path.join(HIP, h) for h in ("cobyla_search.h", "local_common.h", "dev_common.h")] + [os.path.join(ROOT, "include", "nlopt_amd.h")]
-    if os.path.exists(OUT) and all(os.path.getmtime(OUT) > os.path.getmtime(s) for s in deps):
-        return OUT
+def build(alg="nldrmd"):
+    """alg: "nldrmd" (hip/nldrmd_kernels.hip) or "sbplx" (hip/sbplx_kernels.hip, tools/sbplx_emu_check.py): the same search body"""
+    out = OUT.replace("nldrmd", alg)
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    srcs = [os.path.join(HIP, alg + "_kernels.hip")]
+    deps = srcs + [os.path.join(HIP, h) for h in ("nm_search.h", "cobyla_search.h", "local_common.h", "dev_common.h")] + [os.path.join(ROOT, "include", "nlopt_amd.h")]
+    if os.path.exists(out) and all(os.path.getmtime(out) > os.path.getmtime(s) for s in deps):
+        return out
     subprocess.run(["g++", "-O1", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-x", "c++", "-w", "-I", os.path.join(ROOT, "tools", "simt_emu"),
-                    "-o", OUT] + srcs + ["-lpthread"], check=True)
-    return OUT
+                    "-o", out] + srcs + ["-lpthread"], check=True)
+    return out
 
 
-def bind(L):
+def bind(L, alg="nldrmd"):
     vp = C.c_void_p
-    L.nla_nldrmd_serves.restype = C.c_int; L.nla_nldrmd_serves.argtypes = [C.c_int]
-    L.nla_nldrmd_work_doubles.restype = C.c_size_t; L.nla_nldrmd_work_doubles.argtypes = [C.c_int, C.c_int]
-    L.nla_nldrmd_save_bytes.restype = C.c_size_t; L.nla_nldrmd_save_bytes.argtypes = [C.c_int]
-    L.nla_k_nldrmd_batch.restype = C.c_int
-    L.nla_k_nldrmd_batch.argtypes = [C.c_int] * 4 + [vp] * 5 + [C.POINTER(Params), vp, C.POINTER(Ext), vp]
+    serves, work, save, batch = (getattr(L, nm % alg) for nm in ("nla_%s_serves", "nla_%s_work_doubles", "nla_%s_save_bytes", "nla_k_%s_batch"))
+    serves.restype = C.c_int; serves.argtypes = [C.c_int]
+    work.restype = C.c_size_t; work.argtypes = [C.c_int, C.c_int]
+    save.restype = C.c_size_t; save.argtypes = [C.c_int]
+    batch.restype = C.c_int
+    batch.argtypes = [C.c_int] * 4 + [vp] * 5 + [C.POINTER(Params), vp, C.POINTER(Ext), vp]
     return L
 
 
 def run_ext(L, n, starts, lo, hi, evaluate, dx=None, xtol_rel=0.0, xtol_abs=None, x_weights=None, ftol_rel=0.0, ftol_abs=0.0, maxeval=0,
-            minf_max=-np.inf, forced_from=None, timeout_from=None, mem=None, max_steps=100000):
+            minf_max=-np.inf, forced_from=None, timeout_from=None, mem=None, max_steps=100000, alg="nldrmd"):
     """the host side of the coroutine nla_k_nldrmd_batch(NLA_OBJ_EXTERNAL): launch, read req, evaluate every waiting row of EX — with
     `evaluate`, or with evaluate[i] for search i —, launch again with resume = 1 until no search waits.  forced_from / timeout_from = k:
     ext.forced / ext.timeout = 1 from the k-th relaunch on (the first launch is number 0; relaunch k delivers the k-th value).
+    alg = "sbplx": nla_k_sbplx_batch, the same contract.
     `asked`: per search, the points it requested in order; `finished_at`: the launch after which its state was 2; `seen`: the states
     after every launch."""
-    bind(L)
+    bind(L, alg)
+    work_doubles, save_bytes, batch = (getattr(L, nm % alg) for nm in ("nla_%s_work_doubles", "nla_%s_save_bytes", "nla_k_%s_batch"))
     mem = mem or HostMem()
     starts = np.asarray(starts, dtype=np.float64).reshape(-1, n)
     count, ld = starts.shape[0], (n + 1) & ~1
@@ -68,8 +73,8 @@ def run_ext(L, n, starts, lo, hi, evaluate, dx=None, xtol_rel=0.0, xtol_abs=None
     opt = [mem.put(np.asarray(a, dtype=np.float64)) if a is not None else None for a in (dx, xtol_abs, x_weights)]
     bd, bxa, bxw = opt
     # 0xff (NaN) everywhere a starting search must not rely on: it writes its slice and its record before it reads them
-    bw = mem.alloc(8 * L.nla_nldrmd_work_doubles(n, count), 0xff)
-    bsave, breq = mem.alloc(L.nla_nldrmd_save_bytes(n) * count, 0xff), mem.put(np.zeros((count, 2), dtype=np.int32))
+    bw = mem.alloc(8 * work_doubles(n, count), 0xff)
+    bsave, breq = mem.alloc(save_bytes(n) * count, 0xff), mem.put(np.zeros((count, 2), dtype=np.int32))
     bEX, bEG, bEF = mem.put(np.full((count, ld), np.nan)), mem.put(np.full(8, np.nan)), mem.put(np.full(count, np.nan))
     bo = mem.alloc(C.sizeof(Result) * count)
     P = Params(minf_max, ftol_rel, ftol_abs, xtol_rel, maxeval, 0, 1.0, bxa.ptr if bxa else None, bxw.ptr if bxw else None, None, None, 0, None)
@@ -78,7 +83,7 @@ def run_ext(L, n, starts, lo, hi, evaluate, dx=None, xtol_rel=0.0, xtol_abs=None
     while True:
         E.forced = 1 if forced_from is not None and step >= forced_from else 0
         E.timeout = 1 if timeout_from is not None and step >= timeout_from else 0
-        rc = L.nla_k_nldrmd_batch(NLA_OBJ_EXTERNAL, n, ld, count, bl.ptr, bu.ptr, bd.ptr if bd else None, bX.ptr, bw.ptr, C.byref(P), bo.ptr, C.byref(E), None)
+        rc = batch(NLA_OBJ_EXTERNAL, n, ld, count, bl.ptr, bu.ptr, bd.ptr if bd else None, bX.ptr, bw.ptr, C.byref(P), bo.ptr, C.byref(E), None)
         assert rc == 0, rc
         mem.sync()
         state = mem.read(breq, np.int32, 2 * count).reshape(count, 2)[:, 0]
