@@ -391,7 +391,7 @@ def mma_params(p=None):
 
 
 def run_port_mma(obj, n, x0=None, maxeval=0, ftol_rel=0.0, ftol_abs=0.0, xtol_rel=0.0, stopval=None, lb=None, ub=None, params=None,
-                 step=None):
+                 step=None, xtol_abs=None, x_weights=None):
     L = port()
     L.orc_mma_minimize.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                    C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(OrcStop), C.POINTER(OrcMma)]
@@ -405,6 +405,12 @@ def run_port_mma(obj, n, x0=None, maxeval=0, ftol_rel=0.0, ftol_abs=0.0, xtol_re
     st.ftol_rel, st.ftol_abs, st.xtol_rel = ftol_rel, ftol_abs, xtol_rel
     if stopval is not None:
         st.minf_max = stopval
+    ta = None if xtol_abs is None else np.array(xtol_abs, dtype=np.float64)
+    xw = None if x_weights is None else np.array(x_weights, dtype=np.float64)
+    if ta is not None:
+        st.xtol_abs = dptr(ta)
+    if xw is not None:
+        st.x_weights = dptr(xw)
     f = L.orc_objective(OBJ[obj])
     cap = 2 * (maxeval or 200000) + 16          # inner_gradients = 0: up to two calls per counted evaluation
     fbuf = np.zeros(cap)
@@ -420,8 +426,10 @@ def run_port_mma(obj, n, x0=None, maxeval=0, ftol_rel=0.0, ftol_abs=0.0, xtol_re
     return dict(ret=ret, minf=minf.value, x=x, nevals=st.nevals, fseq=fbuf[:rec.len].copy(), xhash=hbuf[:rec.len].copy())
 
 
-def run_ref_mma(obj, n, x0=None, lb=None, ub=None, params=None, step=None, **kw):
-    """the REAL reference's NLOPT_LD_MMA (24)"""
+def run_ref_mma(obj, n, x0=None, lb=None, ub=None, params=None, step=None, setup=None, **kw):
+    """the REAL reference's NLOPT_LD_MMA (24); setup(R, opt): further settings, after the ones here"""
+    more = setup
+
     def setup(R, opt):
         R.nlopt_set_param.argtypes = [C.c_void_p, C.c_char_p, C.c_double]
         R.nlopt_set_initial_step1.argtypes = [C.c_void_p, C.c_double]
@@ -433,6 +441,7 @@ def run_ref_mma(obj, n, x0=None, lb=None, ub=None, params=None, step=None, **kw)
             R.nlopt_set_lower_bounds(opt, dptr(np.array(lb, dtype=np.float64)))
         if ub is not None:
             R.nlopt_set_upper_bounds(opt, dptr(np.array(ub, dtype=np.float64)))
+        return more(R, opt) if more else None
     return run_ref(24, obj, n, 0, 0, x0=x0, setup=setup, **kw)
 
 

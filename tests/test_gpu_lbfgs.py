@@ -10,6 +10,7 @@ import pytest
 
 import _oracle as O
 import nlopt_amd
+import test_lbfgs_emu
 
 pytestmark = pytest.mark.gpu
 
@@ -98,10 +99,7 @@ def test_lbfgs_host_callback_is_served():
 
 
 # ---- the two batch kernels against each other, at the kernel-level C-ABI -------------------------------------------------------
-class _Params(C.Structure):
-    _fields_ = [("minf_max", C.c_double), ("ftol_rel", C.c_double), ("ftol_abs", C.c_double), ("xtol_rel", C.c_double), ("tolg", C.c_double),
-                ("maxeval", C.c_int32), ("exact", C.c_int32), ("sign", C.c_double), ("xtol_abs", C.c_void_p), ("x_weights", C.c_void_p),
-                ("abort", C.c_void_p), ("ftrace", C.c_void_p), ("ftrace_cap", C.c_int64), ("done", C.c_void_p)]
+_Params = test_lbfgs_emu.tool().Params          # nla_lbfgs_params: the one copy (tools/lbfgs_emu_check.py)
 
 
 class _Result(C.Structure):

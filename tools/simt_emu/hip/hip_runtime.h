@@ -51,13 +51,17 @@ inline Barrier &barrier() { static Barrier b; return b; }
 inline uint64_t *xch(int which) { static uint64_t buf[2][1024]; return buf[which]; }
 struct Idx { unsigned x, y, z; };
 }
-static thread_local simt::Idx threadIdx, blockIdx;
-static thread_local simt::Idx blockDim, gridDim;
+/* ONE copy per thread for the whole program (C++17 inline variables), not one per translation unit: the kernels' shared headers define
+ * inline functions with external linkage (dev_common.h nla_xor_lane, nla_obj_wave_reduce ...), of which the linker keeps ONE copy for a
+ * library built from several .hip files — with `static` that copy read the threadIdx of the translation unit it came from, which a
+ * launch from another one never sets (every work-item shuffled as lane 0: tools/lbfgs_emu_check.py's resident kernel, tree sums) */
+inline thread_local simt::Idx threadIdx, blockIdx;
+inline thread_local simt::Idx blockDim, gridDim;
 
 static inline void __syncthreads() { simt::barrier().wait(); }
 /* which of the two exchange buffers the next shuffle / vote of this work-item uses: ONE turn for all of them, whatever the value's type —
  * a turn per type would let a shuffle of ints write the buffer that the shuffle of doubles just before it is still being read from */
-static thread_local int simt_xch_turn = 0;
+inline thread_local int simt_xch_turn = 0;
 template <class T> static inline T __shfl_xor(T v, int mask, int width = 64)
 {
     static_assert(sizeof(T) <= 8, "emulated shuffle: at most 8 bytes");
