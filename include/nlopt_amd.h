@@ -605,7 +605,7 @@ typedef struct { int32_t state, want_grad; } nla_local_req;
 typedef struct {
     nla_local_req *req;            /* count entries */
     double *EX, *EG, *EF;          /* count x ld points; count x ld gradients; count values */
-    void *save;                    /* count x nla_lbfgs_save_bytes() / nla_mma_save_bytes() / nla_cobyla_save_bytes(n) / nla_nldrmd_save_bytes(n) / nla_sbplx_save_bytes(n) */
+    void *save;                    /* count x nla_lbfgs_save_bytes() / nla_mma_save_bytes() / nla_cobyla_save_bytes(n) / nla_nldrmd_save_bytes(n) / nla_sbplx_save_bytes(n) / nla_tnewton_save_bytes() */
     int32_t resume;                /* 0: start the searches; 1: continue those whose evaluation was delivered */
     int32_t forced, timeout;       /* the caller's nlopt_force_stop flag / maxtime verdict at this launch (stop.c:141-159) */
     int32_t pad;
@@ -724,6 +724,28 @@ size_t nla_cobyla_con_save_bytes(int n, int mc);               /* per search, of
 int nla_k_cobyla_batch_ext_con(int n, int ld, int count, const double *lb, const double *ub, const double *dx, double *X,
                                double *work, const nla_cobyla_params *params, nla_lbfgs_result *out, const nla_local_ext *ext,
                                int mi, int me, int ldc, const double *EC, const double *tol, const int32_t *rowmap, void *stream);
+
+/* ---- LD_TNEWTON, _RESTART, _PRECOND, _PRECOND_RESTART (src/algs/luksan/pnet.c), batched (hip/tnewton_kernels.hip) ------------------- */
+size_t nla_tnewton_work_doubles(int ld, int mf, int count);   /* doubles of `work`: ten vectors and 2 mf column scalars per search */
+size_t nla_tnewton_hist_doubles(int ld, int mf, int count);   /* doubles of `hist`: 2 mf ld per search (mf = 0: none) */
+size_t nla_tnewton_save_bytes(void);                          /* per search, of nla_local_ext.save */
+/* replaces: luksan_pnet (pnet.c:567-662 over pnet_, :128-564) for `count` independent starts at once, one workgroup per start, the whole
+ * optimisation loop — the CG iteration with finite-difference Hessian-vector products included — on the device.  mos = algorithm -
+ * NLOPT_LD_TNEWTON (0 .. 3): mos1 = 1 + mos % 2, mos2 = 1 + mos / 2 (optimize.c:733-738).  mf: the preconditioner's history pairs for
+ * mos >= 2 (nla_lbfgs_default_mf's rule, pnet.c:590-594; hist = nla_tnewton_hist_doubles doubles), 0 for mos < 2 (hist may be NULL).
+ * params: LD_LBFGS's record, every field with the same meaning.  X: count x ld, starts in; out: the best value among ALL evaluated points
+ * inside lb / ub (the CG probes included; the first on ties) and its point, as the reference's memoize_func returns them
+ * (optimize.c:460-508,1064-1071); out[i] = (f, nlopt_result, evaluations, PNET's termination code, history columns streamed).
+ * ftrace records every evaluation, probes included.  obj: a compiled-in device objective, or NLA_OBJ_EXTERNAL with `ext` (NULL
+ * otherwise): a coroutine with three evaluation points (first point, probe, line search), want_grad always 1.  With params->exact or
+ * an external objective summed in order, every requested point and the result are the reference's bit for bit.
+ * Refuses with hipErrorInvalidValue, launching nothing: n < 1, ld < n, mos outside 0 .. 3, mf < 1 or hist NULL for mos >= 2, mf != 0 for
+ * mos < 2, a NULL pointer among lb, ub, X, work, iwork, params, out, an external objective without ext or one of ext->req / EX / EG / EF /
+ * save; count <= 0 returns 0.
+ * Out of scope: an LDS-resident variant, these algorithms as MLSL's local optimiser, nonlinear constraints. */
+int nla_k_tnewton_batch(int obj, int n, int ld, int mf, int mos, int count, const double *lb, const double *ub, double *X,
+                        double *work, int *iwork, double *hist, const nla_lbfgs_params *params, nla_lbfgs_result *out,
+                        const nla_local_ext *ext, void *stream);
 
 /* ---- LN_NELDERMEAD (src/algs/neldermead/nldrmd.c), batched (hip/nldrmd_kernels.hip) ----------------------------------------------- */
 /* stopping values as nlopt_stopping holds them; exact / sign / xtol_abs / x_weights (nlopt_stop_x, stop.c:98-108) / abort / ftrace / done

@@ -19,6 +19,7 @@ LIB_PATH = os.environ.get("NLOPT_AMD_LIB") or os.path.join(_HERE, "lib", "libnlo
 GN_CRS2_LM, GN_MLSL, GD_MLSL, GN_MLSL_LDS, GD_MLSL_LDS = 19, 20, 21, 22, 23
 LD_LBFGS, LD_MMA, GN_ISRES, G_MLSL, G_MLSL_LDS, GN_ESCH = 11, 24, 35, 38, 39, 42
 LN_COBYLA, LN_NELDERMEAD, LN_SBPLX = 25, 28, 29
+LD_TNEWTON, LD_TNEWTON_RESTART, LD_TNEWTON_PRECOND, LD_TNEWTON_PRECOND_RESTART = 15, 16, 17, 18
 # nlopt_result values
 FAILURE, INVALID_ARGS, OUT_OF_MEMORY, ROUNDOFF_LIMITED, FORCED_STOP = -1, -2, -3, -4, -5
 SUCCESS, STOPVAL_REACHED, FTOL_REACHED, XTOL_REACHED, MAXEVAL_REACHED, MAXTIME_REACHED = 1, 2, 3, 4, 5, 6
@@ -705,7 +706,7 @@ class Opt:
         return x, minf.value, ret
 
     def optimize_batch(self, X0):
-        """nlopt_amd_optimize_batch: one local search (LD_LBFGS, LD_MMA, LN_COBYLA, LN_NELDERMEAD, LN_SBPLX) from every row of X0, side by side on the device.
+        """nlopt_amd_optimize_batch: one local search (LD_LBFGS, LD_MMA, LN_COBYLA, LN_NELDERMEAD, LN_SBPLX, LD_TNEWTON*) from every row of X0, side by side on the device.
         Nonlinear constraints are served for LN_COBYLA on a user device objective when every one of them is a bound device block
         (add_inequality_device_constraints / add_equality_device_constraints); anything else with constraints is refused.
         Returns (X, minf, results, numevals): the minimisers (count, n) and per search its value, nlopt_result and evaluation count.

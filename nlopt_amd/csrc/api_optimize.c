@@ -169,6 +169,12 @@ static nlopt_result minimize_dispatch(nlopt_opt opt, double *x, double *minf)
         /* every search runs on the device (nldrmd_driver.c); a device layer without the launcher, or n beyond it: not provided, as before */
         if (nla_nldrmd_device_serves((int) n)) return nla_nldrmd_minimize(opt, (int) n, opt->f, opt->f_data, opt->lb, opt->ub, x, minf, &stop);
         goto not_provided;
+    case NLOPT_LD_TNEWTON: case NLOPT_LD_TNEWTON_RESTART: case NLOPT_LD_TNEWTON_PRECOND: case NLOPT_LD_TNEWTON_PRECOND_RESTART:   /* optimize.c:733-738 */
+        if (nla_tnewton_has_launcher())
+            return nla_tnewton_minimize(opt, (int) n, opt->f, opt->f_data, opt->lb, opt->ub, x, minf, &stop, (int) opt->vector_storage,
+                                        1 + (int) (opt->algorithm - NLOPT_LD_TNEWTON) % 2, 1 + (int) (opt->algorithm - NLOPT_LD_TNEWTON) / 2,
+                                        nlopt_get_param(opt, "tolg", 0.));
+        goto not_provided;
     case NLOPT_LN_SBPLX:                                                                 /* optimize.c:886-905 */
         if (nla_sbplx_device_serves((int) n)) return nla_sbplx_minimize(opt, (int) n, opt->f, opt->f_data, opt->lb, opt->ub, x, minf, &stop);
         /* fall through */
@@ -314,6 +320,7 @@ static int objective_stays_on_device(const nlopt_opt opt)
     if (!(nlopt_amd_objective_id(opt->f) >= 0 || nla_userobj_is_adapter(opt->f))) return 0;
     if (a == NLOPT_LD_LBFGS || a == NLOPT_G_MLSL || a == NLOPT_G_MLSL_LDS || (a >= NLOPT_GN_MLSL && a <= NLOPT_GD_MLSL_LDS)) return 1;
     if (a == NLOPT_LD_MMA) return opt->m == 0;
+    if (nla_is_tnewton(a)) return nla_tnewton_has_launcher();       /* (the kernel keeps the best point seen itself) */
     if (a == NLOPT_LN_NELDERMEAD || a == NLOPT_LN_SBPLX) return !fix_applies(opt);      /* (fixed coordinates: the elimination wrapper is a host function) */
     if (a == NLOPT_GN_CRS2_LM || a == NLOPT_GN_ISRES || a == NLOPT_GN_ESCH) {
         if (fix_applies(opt) || nlopt_get_param(opt, "amd_host_eval", 0) != 0) return 0;
@@ -367,9 +374,12 @@ nlopt_result nlopt_optimize(nlopt_opt opt, double *x, double *opt_f)
     opt->force_stop_child = NULL;
     maximize = opt->maximize;
     nla_direction_enter(opt, maximize && objective_stays_on_device(opt), &dir);          /* minimise -f (optimize.c:1014-1024) */
-    if ((memo = opt->algorithm == NLOPT_LN_COBYLA && opt->m == 0 && opt->p == 0)) {
-        /* the reference returns the best FEASIBLE point any objective call of an unconstrained COBYLA run saw, not the
-         * algorithm's own answer (memoize_func, optimize.c:450-508,1026-1036,1064-1071) */
+    /* LD_TNEWTON*: with a host callback only — a device objective never passes through opt->f, and the kernel applies the same rule to
+     * every point it evaluates (hip/tnewton_kernels.hip) */
+    if ((memo = (opt->algorithm == NLOPT_LN_COBYLA || (nla_is_tnewton(opt->algorithm) && nla_tnewton_has_launcher() &&
+                                                       nlopt_amd_objective_id(opt->f) < 0 && !nla_userobj_is_adapter(opt->f))) && opt->m == 0 && opt->p == 0)) {
+        /* the reference returns the best FEASIBLE point any objective call of an unconstrained COBYLA or truncated-Newton run saw, not
+         * the algorithm's own answer (memoize_func, optimize.c:450-508,1026-1036,1064-1071) */
         mm.f = opt->f; mm.f_data = opt->f_data; mm.lb = opt->lb; mm.ub = opt->ub; mm.minf = DBL_MAX;
         mm.bestx = (double *) malloc(sizeof(double) * (opt->n ? opt->n : 1));
         if (!mm.bestx) { nla_set_errmsg(opt, "out of memory"); memo = 0; ret = NLOPT_OUT_OF_MEMORY; computed = 0; goto restore; }

@@ -2,7 +2,7 @@
  *
  * The reference has no counterpart: a caller with many starts, or with many small fits of one shape, loops over nlopt_optimize.  Here
  * the loop is the batch dimension of the kernels that already serve MLSL's local phase — one workgroup (LD_LBFGS, LD_MMA) or one
- * wavefront (LN_COBYLA, LN_NELDERMEAD, LN_SBPLX) per search — behind the same context a lone nlopt_optimize(LD_LBFGS | LD_MMA | LN_NELDERMEAD | LN_SBPLX) runs on with count = 1
+ * wavefront (LN_COBYLA, LN_NELDERMEAD, LN_SBPLX) per search; LD_TNEWTON and its three variants (one workgroup) joined them — behind the same context a lone nlopt_optimize(LD_LBFGS | LD_MMA | LN_NELDERMEAD | LN_SBPLX) runs on with count = 1
  * (local_ctx.c: nla_local_batch_open / nla_local_ctx_run).  Those kernels pick their code path from the objective, n and the
  * parameters, never from the number of searches, which is what makes search i of a batch the lone run from x_i bit for bit.
  *
@@ -57,9 +57,11 @@ nlopt_result nlopt_amd_optimize_batch(nlopt_opt opt, size_t count, double *x, do
     if (count > (size_t) INT_MAX) { nla_set_errmsg(opt, "nlopt_amd_optimize_batch: count > INT_MAX"); return NLOPT_INVALID_ARGS; }
     if (!opt->f || n == 0) { nla_set_errmsg(opt, "nlopt_amd_optimize_batch: no objective set, or n == 0"); return NLOPT_INVALID_ARGS; }
     spec.alg = opt->algorithm == NLOPT_LD_LBFGS ? NLA_LOCAL_LBFGS : opt->algorithm == NLOPT_LD_MMA ? NLA_LOCAL_MMA : opt->algorithm == NLOPT_LN_COBYLA ? NLA_LOCAL_COBYLA :
-               opt->algorithm == NLOPT_LN_NELDERMEAD ? NLA_LOCAL_NLDRMD : opt->algorithm == NLOPT_LN_SBPLX ? NLA_LOCAL_SBPLX : -1;
+               opt->algorithm == NLOPT_LN_NELDERMEAD ? NLA_LOCAL_NLDRMD : opt->algorithm == NLOPT_LN_SBPLX ? NLA_LOCAL_SBPLX :
+               nla_is_tnewton(opt->algorithm) && nla_tnewton_has_launcher() ? NLA_LOCAL_TNEWTON : -1;
     if (spec.alg < 0) {
-        nla_set_errmsg(opt, "nlopt_amd_optimize_batch serves NLOPT_LD_LBFGS, NLOPT_LD_MMA, NLOPT_LN_COBYLA, NLOPT_LN_NELDERMEAD and NLOPT_LN_SBPLX, not %s", nlopt_algorithm_to_string(opt->algorithm));
+        nla_set_errmsg(opt, "nlopt_amd_optimize_batch serves NLOPT_LD_LBFGS, NLOPT_LD_MMA, NLOPT_LN_COBYLA, NLOPT_LN_NELDERMEAD and NLOPT_LN_SBPLX, not %s (and NLOPT_LD_TNEWTON with its three variants on a device layer that has their launcher)",
+                       nlopt_algorithm_to_string(opt->algorithm));
         return NLOPT_INVALID_ARGS;
     }
     if (opt->m > 0 || opt->p > 0) {
@@ -160,6 +162,11 @@ nlopt_result nlopt_amd_optimize_batch(nlopt_opt opt, size_t count, double *x, do
     opt->batch_con_launches = 0;
     spec.con = con; spec.ncon = ncon; spec.ncon_eq = ncon ? (int) opt->p : 0; spec.mi = mi; spec.me = me; spec.con_tol = con_tol;
     spec.con_launches = &opt->batch_con_launches;
+    if (nla_is_tnewton(opt->algorithm)) {                /* as nla_tnewton_minimize sets a lone run up */
+        spec.mos = (int) opt->algorithm - (int) NLOPT_LD_TNEWTON;
+        prm.tolg = nlopt_get_param(opt, "tolg", 0.);
+        spec.mf = spec.mos >= 2 ? nla_lbfgs_default_mf((int) n, (int) opt->vector_storage, stop.maxeval) : 0;
+    }
     if (opt->algorithm == NLOPT_LD_LBFGS) { prm.tolg = nlopt_get_param(opt, "tolg", 0.); spec.mf = nla_lbfgs_default_mf((int) n, (int) opt->vector_storage, stop.maxeval); }
 
     /* the chunk: what fits half of the free memory (the other half is the caller's, and the allocator's slack) */

@@ -31,6 +31,7 @@
 #include "local_common.h"
 #include <limits.h>
 #include "../lbfgs_scalar.h"
+#include "luksan_bounds.h"
 #include "../../../include/nlopt_amd.h"
 
 /* scalar state of one search across an external evaluation (everything else lives in the instance's vectors) */
@@ -41,26 +42,6 @@ struct lb_saved {
 };
 
 #define LB_EPT 16                  /* coordinates per thread held in registers by the direction loops (n <= 4096) */
-
-__device__ __forceinline__ void lb_project(int n, double *x, const int *ix, const double *xl, const double *xu, double eps9)   /* pcbs04 */
-{
-    for (int i = threadIdx.x; i < n; i += LB_T) {
-        const int t = ix[i] < 0 ? -ix[i] : ix[i];
-        double v = x[i];
-        if ((t == 1 || t == 3 || t == 4) && v <= xl[i] + eps9 * LB_MAX(fabs(xl[i]), 1.)) v = xl[i];
-        if ((t == 2 || t == 3 || t == 4) && v >= xu[i] - eps9 * LB_MAX(fabs(xu[i]), 1.)) v = xu[i];
-        x[i] = v;
-    }
-}
-__device__ __forceinline__ void lb_add_active(int n, double *x, int *ix, const double *xl, const double *xu)                 /* pyadc0 */
-{
-    for (int i = threadIdx.x; i < n; i += LB_T) {
-        const int ii = ix[i], t = ii < 0 ? -ii : ii;
-        if (t >= 5) ix[i] = -t;
-        else if ((t == 1 || t == 3 || t == 4) && x[i] <= xl[i]) { x[i] = xl[i]; ix[i] = (t == 4) ? -3 : -t; }
-        else if ((t == 2 || t == 3 || t == 4) && x[i] >= xu[i]) { x[i] = xu[i]; ix[i] = (t == 3) ? -4 : -t; }
-    }
-}
 
 /* The two Strang loops (mxdrcb / mxdrcf, mssubs.c:353-441) with the direction held in REGISTERS (thread t owns coordinates t, t+256, ...:
  * the same partial-sum order as lb_mdot) and the next history column prefetched while the current dot product is being reduced — one

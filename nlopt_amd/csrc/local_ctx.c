@@ -1,8 +1,8 @@
 /* local_ctx.c — the batch context of the local optimisers (nla_local_ctx): device buffers for up to `cap` simultaneous searches by
  * LD_LBFGS (hip/lbfgs_kernels.hip), LD_MMA (hip/mma_kernels.hip) or LN_COBYLA (bound constraints only: hip/cobyla_kernels.hip,
  * cobyla_global.hip, cobyla_ext.hip; nonlinear constraints from a user's device blocks: cobyla_con.hip) or LN_NELDERMEAD / LN_SBPLX
- * (hip/nldrmd_kernels.hip, hip/sbplx_kernels.hip), and the loop that runs them.  Its callers: a lone nlopt_optimize(LD_LBFGS | LD_MMA | LN_NELDERMEAD | LN_SBPLX) with count = 1
- * (nla_local_minimize_one below, behind lbfgs_driver.c / mma_driver.c / nldrmd_driver.c), MLSL's local phase with one workgroup or wavefront per start
+ * (hip/nldrmd_kernels.hip, hip/sbplx_kernels.hip) or LD_TNEWTON and its three variants (hip/tnewton_kernels.hip), and the loop that runs them.  Its callers: a lone nlopt_optimize(LD_LBFGS | LD_MMA | LN_NELDERMEAD | LN_SBPLX) with count = 1
+ * (nla_local_minimize_one below, behind lbfgs_driver.c / mma_driver.c / nldrmd_driver.c; tnewton_driver.c), MLSL's local phase with one workgroup or wavefront per start
  * (mlsl_driver.c), nlopt_amd_optimize_batch (batch_driver.c).  What differs between the algorithms is one entry of the table ALGS.
  *
  * Three kinds of objective (nla_evaluator):
@@ -37,7 +37,7 @@ typedef struct {
 enum { B_X, B_RES, B_REQ, B_EX, B_EG, B_EF, B_LIST, B_SAVE, B_WORK, B_IWORK, B_HIST, B_EC, B_COUNT };
 
 struct nla_local_ctx {
-    int alg, n, ld, cap, mf;
+    int alg, n, ld, cap, mf, mos;
     const local_alg *a;
     nla_evaluator ev;
     nla_mma_params mma;            /* LD_MMA: the algorithm's own parameters (the stopping values come with each run) */
@@ -154,6 +154,19 @@ static int sbplx_launch(nla_local_ctx *c, int obj, int count, const nla_lbfgs_pa
     return nla_k_sbplx_batch(obj, c->n, c->ld, count, c->d_lb, c->d_ub, c->d_sigma_init, c->d_X, c->d_work, &M, c->d_res, ext, c->st);
 }
 
+/* LD_TNEWTON and its variants: ten vectors per search in `work`, the preconditioner's history (mf = 0 for the ids without one: none) */
+static size_t tnewton_save(int n) { (void) n; return nla_tnewton_save_bytes ? nla_tnewton_save_bytes() : 0; }
+SIZES(tnewton_sizes)
+{
+    (void) kind; (void) n;
+    if (!nla_tnewton_has_launcher()) return;
+    *work = nla_tnewton_work_doubles(ld, mf, cap); *iwork = (size_t) ld * (size_t) cap; *hist = nla_tnewton_hist_doubles(ld, mf, cap);
+}
+static int tnewton_launch(nla_local_ctx *c, int obj, int count, const nla_lbfgs_params *P, const nla_local_ext *ext)
+{
+    return nla_k_tnewton_batch(obj, c->n, c->ld, c->mf, c->mos, count, c->d_lb, c->d_ub, c->d_X, c->d_work, c->d_iwork, c->d_hist, P, c->d_res, ext, c->st);
+}
+
 static const local_alg ALGS[] = {
     /* (history columns streamed twice + the point written and read once per evaluation; mma_kernels.hip header; the point again) */
     [NLA_LOCAL_LBFGS]  = { lbfgs_save,  lbfgs_sizes,  1, lbfgs_launch,  32, 16 },
@@ -161,6 +174,10 @@ static const local_alg ALGS[] = {
     [NLA_LOCAL_COBYLA] = { cobyla_save, cobyla_sizes, 0, cobyla_launch, 0,  16 },   /* (never wants a gradient) */
     [NLA_LOCAL_NLDRMD] = { nldrmd_save, nldrmd_sizes, 0, nldrmd_launch, 0,  16 },   /* (never wants a gradient; the point, as LN_COBYLA counts it) */
     [NLA_LOCAL_SBPLX]  = { sbplx_save,  sbplx_sizes,  0, sbplx_launch,  0,  16 },   /* (the same) */
+    /* per preconditioner column a dot and an axpy pass (16 n bytes; cols counts both recurrences of every application); per evaluation —
+     * most are CG probes — the probe written and read, the quotient pass (3 vectors), the fused CG step (4 read, 2 written), <xs, xs>
+     * and the direction update (3): 14 vectors of 8 n bytes */
+    [NLA_LOCAL_TNEWTON] = { tnewton_save, tnewton_sizes, 1, tnewton_launch, 16, 112 },
 };
 
 /* THE layout: the size of every device buffer of a context for `cap` searches.  Allocation (nla_local_ctx_create) and the chunk size of
@@ -253,7 +270,7 @@ done:
 }
 
 /* the context of *s (nla_internal.h); NULL: out of memory, or LN_COBYLA for a host callback or a dimension no device launcher serves, or
- * LN_NELDERMEAD / LN_SBPLX on a device layer without its launcher or at a dimension it does not serve, or
+ * LN_NELDERMEAD / LN_SBPLX on a device layer without its launcher or at a dimension it does not serve, or LD_TNEWTON* without its launcher, or
  * constraint blocks for anything but LN_COBYLA on a user's objective at an (n, mc) the constrained launcher serves */
 nla_local_ctx *nla_local_ctx_create(const nla_local_spec *s)
 {
@@ -264,11 +281,12 @@ nla_local_ctx *nla_local_ctx_create(const nla_local_spec *s)
     if (s->alg == NLA_LOCAL_COBYLA && !nla_cobyla_device_serves(kind, s->n)) return NULL;
     if (s->alg == NLA_LOCAL_NLDRMD && !nla_nldrmd_device_serves(s->n)) return NULL;
     if (s->alg == NLA_LOCAL_SBPLX && !nla_sbplx_device_serves(s->n)) return NULL;
+    if (s->alg == NLA_LOCAL_TNEWTON && (!nla_tnewton_has_launcher() || s->mos < 0 || s->mos > 3 || (s->mos >= 2 ? s->mf < 1 : s->mf != 0))) return NULL;
     if (s->ncon > 0 && (s->alg != NLA_LOCAL_COBYLA || kind != NLA_EVAL_USER || !s->con || !s->con_tol || s->mi < 0 || s->me < 0 ||
                         !nla_cobyla_con_device_serves(s->n, s->mi + 2 * s->me))) return NULL;
     c = (nla_local_ctx *) calloc(1, sizeof *c);
     if (!c) return NULL;
-    c->alg = s->alg; c->a = &ALGS[s->alg]; c->ev = *s->ev; c->n = s->n; c->ld = (s->n + 1) & ~1; c->cap = s->cap; c->mf = s->mf;
+    c->alg = s->alg; c->a = &ALGS[s->alg]; c->ev = *s->ev; c->n = s->n; c->ld = (s->n + 1) & ~1; c->cap = s->cap; c->mf = s->mf; c->mos = s->mos;
     if (s->mma) c->mma = *s->mma;
     c->d_sigma_init = s->d_step; c->d_lb = s->d_lb; c->d_ub = s->d_ub; c->st = s->stream;
     local_layout(b, s->alg, kind, s->n, s->mf, s->cap, s->ncon > 0 ? s->mi : 0, s->ncon > 0 ? s->me : 0);

@@ -282,7 +282,7 @@ nlopt_result nla_isres_minimize(nlopt_opt opt, int n, nlopt_func f, void *f_data
 int nla_lbfgs_default_mf(int n, int mf, int maxeval);
 
 /* ---- the batch context of the local optimisers (local_ctx.c) ---------------------------------------------------------------------- */
-enum { NLA_LOCAL_LBFGS = 0, NLA_LOCAL_MMA = 1, NLA_LOCAL_COBYLA = 2, NLA_LOCAL_NLDRMD = 3, NLA_LOCAL_SBPLX = 4 };
+enum { NLA_LOCAL_LBFGS = 0, NLA_LOCAL_MMA = 1, NLA_LOCAL_COBYLA = 2, NLA_LOCAL_NLDRMD = 3, NLA_LOCAL_SBPLX = 4, NLA_LOCAL_TNEWTON = 5 };
 typedef struct nla_local_ctx nla_local_ctx;
 /* what a context is created from.  LN_COBYLA (bound constraints only) gives NULL for a host callback or a dimension no device launcher
  * serves (nla_cobyla_device_serves below) */
@@ -290,7 +290,7 @@ typedef struct {
     int alg;                            /* NLA_LOCAL_* */
     const nla_evaluator *ev;
     int n, cap;                         /* up to cap simultaneous searches */
-    int mf;                             /* LD_LBFGS: history pairs */
+    int mf;                             /* LD_LBFGS: history pairs; LD_TNEWTON*: the preconditioner's pairs, 0 for the two ids without one */
     const nla_mma_params *mma;          /* LD_MMA: the algorithm's parameters (mma_driver.c reads them) */
     const double *d_step;               /* LD_MMA, LN_COBYLA, LN_NELDERMEAD, LN_SBPLX: the initial step on the device, or NULL = the default step of every start (options.c:921-946) */
     const double *d_lb, *d_ub;          /* the box on the device (uploaded before the call: LN_COBYLA reads it back) */
@@ -302,6 +302,7 @@ typedef struct {
     int ncon, ncon_eq, mi, me;
     const double *con_tol;
     uint64_t *con_launches;             /* optional: incremented per launch of a block */
+    int mos;                            /* LD_TNEWTON*: algorithm - NLOPT_LD_TNEWTON (mos1 = 1 + mos % 2, mos2 = 1 + mos / 2, optimize.c:733-738) */
 } nla_local_spec;
 nla_local_ctx *nla_local_ctx_create(const nla_local_spec *spec);
 void nla_local_ctx_set_cobyla_min_batch(nla_local_ctx *c, int min_batch);
@@ -355,6 +356,13 @@ extern __typeof(nla_sbplx_work_doubles) nla_sbplx_work_doubles __attribute__((we
 extern __typeof(nla_sbplx_save_bytes) nla_sbplx_save_bytes __attribute__((weak));
 static inline int nla_sbplx_has_launcher(void) { return nla_k_sbplx_batch && nla_sbplx_serves && nla_sbplx_work_doubles && nla_sbplx_save_bytes; }
 static inline int nla_sbplx_device_serves(int n) { return nla_sbplx_has_launcher() && nla_sbplx_serves(n); }
+/* device LD_TNEWTON and its three variants (hip/tnewton_kernels.hip), the same way: any n */
+extern __typeof(nla_k_tnewton_batch) nla_k_tnewton_batch __attribute__((weak));
+extern __typeof(nla_tnewton_work_doubles) nla_tnewton_work_doubles __attribute__((weak));
+extern __typeof(nla_tnewton_hist_doubles) nla_tnewton_hist_doubles __attribute__((weak));
+extern __typeof(nla_tnewton_save_bytes) nla_tnewton_save_bytes __attribute__((weak));
+static inline int nla_tnewton_has_launcher(void) { return nla_k_tnewton_batch && nla_tnewton_work_doubles && nla_tnewton_hist_doubles && nla_tnewton_save_bytes; }
+static inline int nla_is_tnewton(nlopt_algorithm a) { return a >= NLOPT_LD_TNEWTON && a <= NLOPT_LD_TNEWTON_PRECOND_RESTART; }
 /* the waiting list of a coroutine step built on the device (hip/local_list.hip) and the free-memory query nlopt_amd_optimize_batch
  * sizes its chunks from, reached the same way: without them the host loop builds the list and the chunk size is a fixed guess */
 extern __typeof(nla_k_local_waiting_list) nla_k_local_waiting_list __attribute__((weak));
@@ -395,6 +403,9 @@ nlopt_result nla_local_minimize_one(int alg, nlopt_opt opt, int n, nlopt_func f,
 nlopt_result nla_local_minimize_one_res(int alg, nlopt_opt opt, int n, nlopt_func f, void *f_data, const double *lb, const double *ub, double *x,
                                         double *minf, nla_stopping *stop, int mf, double tolg, const nla_mma_params *mma, const double *step,
                                         nla_lbfgs_result *res_out);
+/* NLOPT_LD_TNEWTON* (tnewton_driver.c; reference entry luksan_pnet, pnet.c:567-662) */
+nlopt_result nla_tnewton_minimize(nlopt_opt opt, int n, nlopt_func f, void *f_data, const double *lb, const double *ub, double *x, double *minf,
+                                  nla_stopping *stop, int mf, int mos1, int mos2, double tolg);
 /* NLOPT_LN_NELDERMEAD (nldrmd_driver.c; reference entry nldrmd_minimize, nldrmd.c:290-314) */
 nlopt_result nla_nldrmd_minimize(nlopt_opt opt, int n, nlopt_func f, void *f_data, const double *lb, const double *ub, double *x, double *minf,
                                  nla_stopping *stop);
